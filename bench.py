@@ -1,13 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the spatial-VAE ELBO training step on MI355X (BASELINE.json metric).
 
-    python bench.py [--config 2] [--gpus N] [--scaling weak|strong] [--steps K] [--warmup W]
+    python bench.py [--config 2] [--gpus N] [--scaling weak|strong] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" = forward + backward + Adam step of the ELBO on one minibatch (train_mnist.py:143-150 of the reference and its
 siblings in train_galaxy.py / train_particles.py).  --config picks the BASELINE.json configuration (default 2, the one
 the metric is quoted on: rotated+translated MNIST shape 28x28, z=2, p/q hidden 500 x 2, tanh, batch 256); 1, 3, 4, 5 are
-the other BASELINE configs at their full sizes.  Inputs are synthetic (there are no datasets here) and resident in HBM
-before the timed region.  Rank 0 prints ONE JSON line.
+the other BASELINE configs at their full sizes.  Inputs are synthetic (there are no datasets here), seeded (the same
+arguments give the same inputs on every run) and resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the line: `value` (images/s), `ms_per_step` and the
+workload; `roofline` and `cpu_baseline` are null there.  --full adds everything below (per-kernel HIP events in the timed
+steps, extra steps for the per-kernel breakdown, the sustained run, the CPU baseline, the fp16x3 child process).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned -- the (global) metrics `elbo`,
+`log_p_x_g_z`, `kl_div`, the reconstruction `y_hat` (mnist / galaxy scripts) and every parameter after the Adam update
+(`p_net.<name>`, `q_net.<name>`) -- as DIR/<name>.npy, float32.  At most 64 MB in all: when the arrays exceed it, the largest
+ones are cut to a fixed seeded sample of their flattened elements (the same indices on every run).
 
 --gpus N > 1: one process per GPU.  Launched plainly (`python bench.py --gpus N`) this process starts the N ranks itself
 -- fresh interpreters, started BEFORE anything here touches the GPU, with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set --
@@ -16,7 +25,7 @@ config's batch PER GPU (global batch = N x batch); --scaling strong: the config'
 contiguously over the ranks.  Either way each rank's gradient enters the all-reduce weighted by
 local/global rows (spatial_vae_amd/dp.py: one all-reduce per step; two buckets, the decoder's on a side stream, for heavy encoders).
 
-The line also carries
+With --full the line also carries
   roofline     : the dominant kernel (an fp32-MFMA GEMM of a decoder hidden layer) -- algorithmic FLOPs per launch / its
                  average launch duration, the durations taken live from HIP events recorded on the launch stream during
                  the timed steps (svae_profile_* in include/svae.h); peak = 157.3 TFLOP/s fp32 MFMA.  `traffic` is the
@@ -241,7 +250,7 @@ def secondary_mode(args):
     """The same workload in a child process with --gemm fp16x3 (the mode is fixed per process)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gemm", "fp16x3", "--steps", str(args.steps), "--warmup",
-           str(args.warmup), "--config", str(args.config), "--no-cpu-baseline", "--no-secondary", "--sustained", "0"]
+           str(args.warmup), "--config", str(args.config), "--full", "--no-cpu-baseline", "--no-secondary", "--sustained", "0"]
     try:
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
         line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]
@@ -272,7 +281,49 @@ def parse_args(argv=None):
     ap.add_argument("--sustained", type=float, default=10.0,
                     help="N=1: after the timed window keep stepping for at least this many seconds and report the rate and the "
                          "GEMM averages under sustained load (0 = skip)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel events and breakdown (roofline), the "
+                         "sustained run, the CPU baseline and the fp16x3 mode (the --no-* / --sustained options trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6 - 64 * 1024    # 64 MB in all, less room for the .npy headers
+
+
+def step_outputs(step, out):
+    """{name: tensor} a caller of the timed step holds after it: the global (elbo, log_p, kl), y_hat when the script
+    returns it, and every parameter after the update."""
+    arrays = {"elbo": step.metrics[0:1], "log_p_x_g_z": step.metrics[1:2], "kl_div": step.metrics[2:3]}
+    if out is not None and len(out) > 3:
+        arrays["y_hat"] = out[3]
+    for prefix, net in (("p_net", step.p_net), ("q_net", step.q_net)):
+        for name, p in net.named_parameters():
+            arrays["%s.%s" % (prefix, name)] = p
+    return arrays
+
+
+def dump_outputs(directory, arrays, budget_bytes=DUMP_BUDGET_BYTES):
+    """DIR/<name>.npy in float32.  Smallest arrays first, each given an equal share of what is left of the budget; an array
+    above its share becomes a sorted sample of its flattened elements drawn from a fixed seed (identical on every run)."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    left = budget_bytes // 4
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        t = t.detach()
+        if t.numel() > share:
+            idx = torch.randint(t.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.size
 
 
 def main():
@@ -346,13 +397,15 @@ def main():
     comm_pairs = []
 
     def run(k, timed=False):
+        out = None
         for i in range(k):  # each rank holds local_B of the global minibatch: its gradient enters the all-reduce with that weight
             if timed and dp.collectives_on():
                 pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 step.comm_events = pair
                 comm_pairs.append(pair)
-            step(x, *batch(i), weight=weight, global_batch=global_B)
+            out = step(x, *batch(i), weight=weight, global_batch=global_B)
         step.comm_events = None
+        return out
 
     if args.graph:
         if world > 1:
@@ -363,17 +416,19 @@ def main():
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
     if profile:
         _lib.profile_enable(1)  # HIP events around the three GEMM kernels only: ~6 event pairs per step
         _lib.profile_read()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(args.steps, timed=True)
+    last = run(args.steps, timed=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:     # before any untimed step of --full moves the parameters on
+        dump_outputs(args.dump_outputs, step_outputs(step, last))
     prof = _lib.profile_read() if profile else {}
     _lib.profile_enable(0)
     comm_ms = [a.elapsed_time(b) for a, b in comm_pairs]
@@ -386,7 +441,7 @@ def main():
         breakdown = {k: round(v[0] / n, 4) for k, v in sorted(_lib.profile_read().items())}
         _lib.profile_enable(0)
     sustained = None
-    if world == 1 and args.sustained > 0 and not args.graph:
+    if args.full and world == 1 and args.sustained > 0 and not args.graph:
         # the timed window above is tens of milliseconds; this shows the rate the chip HOLDS: >= --sustained seconds of
         # back-to-back steps (synchronised every chunk so that the host clock is the device's), then one more chunk with the
         # GEMM events on
@@ -466,7 +521,7 @@ def main():
             # large encoder layers: the factors (x, dy) of dW are all-gathered and dW formed locally (dp.LowRankExchange)
             out["allgather"] = {"bytes_per_step": step._lowrank.bytes_last, "layers": sorted(step._lowrank.keys),
                                 "replaces_allreduce_bytes": out["allreduce"]["gradient_bytes"] - out["allreduce"]["bytes_per_step"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds, ctf_filters.cpu() if ctf_filters is not None else None)
         else:
             out["cpu_baseline"] = None
@@ -475,7 +530,7 @@ def main():
                 ms_k = sustained["gemm_kernels_avg_ms"][roofline["kernel"]]
                 sustained["roofline_frac"] = round(f_gemm * (3 if split else 1) / (ms_k * 1e-3) / 1e12 / roofline["peak"], 4)
             out["sustained"] = sustained
-        if world == 1 and not split and not args.no_secondary and args.config == 2:
+        if args.full and world == 1 and not split and not args.no_secondary and args.config == 2:
             out["fp16x3_mode"] = secondary_mode(args)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -139,6 +139,25 @@ def test_bench_flop_accounting_matches_baseline_md():
     assert bench.inf_dim(bench.CONFIGS[1]) == 3 and bench.inf_dim(bench.CONFIGS[5]) == 11
 
 
+def test_bench_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path):
+    """bench.dump_outputs: float32 .npy per array, small arrays whole, the largest cut to a sample that is the same on
+    every call, everything within the byte budget."""
+    import bench
+    g = torch.Generator().manual_seed(1)
+    arrays = {"elbo": torch.tensor([-3.5]), "w": torch.randn(40, 30, generator=g),
+              "big": torch.randn(5000, generator=g, dtype=torch.float64)}
+    budget = 4 * 3000
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), arrays, budget_bytes=budget)
+    a = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    b = {f[:-4]: np.load(str(tmp_path / "b" / f)) for f in os.listdir(str(tmp_path / "b"))}
+    assert set(a) == {"elbo", "w", "big"} and all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["elbo"], [-3.5]) and np.array_equal(a["w"], arrays["w"].numpy())
+    assert a["big"].shape == (3000 - 1 - 1200,) and np.array_equal(a["big"], b["big"])
+    assert np.isin(a["big"], arrays["big"].numpy().astype(np.float32)).all()
+    assert sum(v.nbytes for v in a.values()) <= budget
+
+
 def test_bench_starts_its_own_ranks_and_reports_their_failure():
     """`python bench.py --gpus 2` without torchrun spawns two ranks itself; with no GPU here both fail at device selection and
     the parent must come back non-zero instead of hanging (on the GPU box tests/test_gpu_bench.py sees the JSON line)."""

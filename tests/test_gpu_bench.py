@@ -26,8 +26,8 @@ def _bench(extra, share=False):
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_two_ranks_from_a_plain_invocation(scaling):
-    d = _bench(["--gpus", "2", "--config", "1", "--steps", "3", "--warmup", "2", "--scaling", scaling, "--no-cpu-baseline",
-                "--no-secondary"], share=True)
+    d = _bench(["--gpus", "2", "--config", "1", "--steps", "3", "--warmup", "2", "--scaling", scaling, "--full",
+                "--no-cpu-baseline", "--no-secondary"], share=True)
     assert d["n_gpus"] == 2 and d["scaling"] == scaling and d["steps"] == 3 and d["value"] > 0
     assert d["config"]["global_batch"] == (128 if scaling == "weak" else 64)
     assert d["config"]["per_gpu_batch"] == (64 if scaling == "weak" else 32)
@@ -41,7 +41,8 @@ def test_two_ranks_from_a_plain_invocation(scaling):
 
 
 def test_single_gpu_line_carries_roofline_and_cpu_baseline():
-    d = _bench(["--config", "1", "--steps", "5", "--warmup", "2", "--cpu-seconds", "2", "--no-secondary", "--sustained", "1.5"])
+    d = _bench(["--config", "1", "--steps", "5", "--warmup", "2", "--full", "--cpu-seconds", "2", "--no-secondary",
+                "--sustained", "1.5"])
     s = d["sustained"]          # >= 1.5 s of back-to-back steps after the timed window
     # (a 5-step window at 0.9 ms per step is mostly the pipeline filling behind the synchronisation: the sustained rate is up
     # to twice that line's value; the bound only catches a wrong unit or a wrong step count)
@@ -56,12 +57,32 @@ def test_single_gpu_line_carries_roofline_and_cpu_baseline():
     assert "median" in c["sample"] and "2 warm-up" in c["sample"]
 
 
+def test_plain_line_times_the_steps_and_dumps_repeat(tmp_path):
+    """A plain run carries the headline only (the extras are --full's) and times exactly --steps steps; --dump-outputs writes
+    the last timed step's metrics, y_hat and updated parameters, identical from run to run with the same arguments."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        d = _bench(["--config", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(out)])
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["dtype"] == "f32" and d["unit"] == "images/s"
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 64) < 0.1                   # batch 64 per step
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "sustained" not in d and "fp16x3_mode" not in d
+        dumps.append({f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))})
+    a, b = dumps
+    assert {"elbo", "log_p_x_g_z", "kl_div", "y_hat", "p_net.layers.1.weight", "q_net.layers.0.weight"} <= set(a) == set(b)
+    assert a["y_hat"].shape == (64, 784) and np.isfinite(a["elbo"]).all()
+    for name in a:
+        assert a[name].dtype == np.float32 and np.array_equal(a[name], b[name]), name
+
+
 @pytest.mark.parametrize("config,batch,kernel_min_frac", [(3, 512, 0.5), (4, 128, 0.6), (5, 256, 0.5)])
 def test_every_baseline_config_has_a_bench_line(config, batch, kernel_min_frac):
     """`bench.py --config N` runs BASELINE configs 3 (fit-noise particles), 4 (galaxy RGB, three hidden layers, the 271 M
     parameter encoder that stays with the vendor GEMM) and 5 (particles with CTF filters built on the device) at their full
     sizes and reports the dominant GEMM against the fp32-MFMA peak."""
-    d = _bench(["--config", str(config), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--sustained", "0"])
+    d = _bench(["--config", str(config), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary",
+                "--sustained", "0"])
     assert d["config"]["baseline_config"] == config and d["config"]["global_batch"] == batch
     assert d["value"] > 0 and d["dtype"] == "f32"
     r = d["roofline"]

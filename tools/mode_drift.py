@@ -12,6 +12,7 @@ import math
 import os
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -54,12 +55,13 @@ def main():
         return child(args.child, args.steps, args.out)
     import numpy as np
     res = {}
-    for mode in ("fp32", "fp16x3"):
-        out = "/tmp/mode_drift_%s.npz" % mode
-        subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--steps", str(args.steps), "--out", out],
-                       check=True, cwd=ROOT)
-        with np.load(out) as f:
-            res[mode] = (f["elbo"], f["params"])
+    with tempfile.TemporaryDirectory() as tmp:      # private to this run: a shared fixed path may belong to someone else
+        for mode in ("fp32", "fp16x3"):
+            out = os.path.join(tmp, "mode_drift_%s.npz" % mode)
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode, "--steps", str(args.steps), "--out", out],
+                           check=True, cwd=ROOT)
+            with np.load(out) as f:
+                res[mode] = (f["elbo"], f["params"])
     (e0, p0), (e1, p1) = res["fp32"], res["fp16x3"]
     rel = np.abs(e1 - e0) / np.abs(e0)
     print(json.dumps({"steps": args.steps, "elbo_first": float(e0[0]), "elbo_last_fp32": float(e0[-1]), "elbo_last_fp16x3": float(e1[-1]),
