@@ -318,6 +318,10 @@ const char* svae_profile_kind_name(int kind);
  * Which kernel families the calls of this process have dispatched so far: the GEMM mode is a request and the plan decides
  * per geometry (fp16x3 takes the fp32 kernels for ReLU-type activations and odd tile counts; the output-layer backward has a
  * streaming, a split, a rank-1 and a generic fused form), so a caller -- or a test -- can tell which code actually ran.
+ * The hidden-layer GEMM's launch form is chosen from the size of the launch: "dense4" counts every dense4_kernel launch,
+ * "dense4_nt2" those with 64-column blocks (dense4_kernel<2> or the wide part of dense4_dual_kernel), "dense4_dual" the
+ * dense4_dual_kernel launches (with or without a half-width tail part; "dense4_tail" those with one), "dense4_cf" the
+ * forward launches whose epilogue contracts the output layer's logits.
  * counts[path] = launches of that family since process start (or since the last read with reset != 0); svae_path_name gives
  * the label ("dense_fp32_fwd", "dense_split_fwd", "wgrad_split", "out_bwd_rank1", ...; "" for unused slots).
  */

@@ -323,10 +323,12 @@ static_assert(K_COUNT <= SVAE_PROF_KINDS, "svae_profile_read arrays too small");
 // geometry (fp16x3 falls back to the fp32 kernels for unbounded activations and odd tile counts), and a test must be able
 // to tell a run of the split kernels from a silent fallback
 enum Path { P_DENSE_FP32_FWD = 0, P_DENSE_FP32_DGRAD, P_WGRAD_FP32, P_DENSE_SPLIT_FWD, P_DENSE_SPLIT_DGRAD, P_WGRAD_SPLIT,
-            P_OUT_BWD_STREAM, P_OUT_BWD_SPLIT, P_OUT_BWD_RANK1, P_OUT_BWD_FUSED_GENERIC, P_DENSE4, P_DENSE4_TAIL, P_WGRAD2, P_COUNT };
+            P_OUT_BWD_STREAM, P_OUT_BWD_SPLIT, P_OUT_BWD_RANK1, P_OUT_BWD_FUSED_GENERIC, P_DENSE4, P_DENSE4_TAIL, P_WGRAD2,
+            P_DENSE4_NT2, P_DENSE4_DUAL, P_DENSE4_CF, P_COUNT };
 const char* const kPathNames[SVAE_PATH_KINDS] = {"dense_fp32_fwd", "dense_fp32_dgrad", "wgrad_fp32", "dense_split_fwd",
                                                   "dense_split_dgrad", "wgrad_split", "out_bwd_stream", "out_bwd_split",
-                                                  "out_bwd_rank1", "out_bwd_fused_generic", "dense4", "dense4_tail", "wgrad2", "", "", ""};
+                                                  "out_bwd_rank1", "out_bwd_fused_generic", "dense4", "dense4_tail", "wgrad2",
+                                                  "dense4_nt2", "dense4_dual", "dense4_cf"};
 static_assert(P_COUNT <= SVAE_PATH_KINDS, "svae_path_counts array too small");
 std::atomic<long long> g_path[SVAE_PATH_KINDS];
 inline void took(int path) { g_path[path].fetch_add(1, std::memory_order_relaxed); }
@@ -742,6 +744,8 @@ DenseBlocks launch_dense(const Geo& g, const DenseArgs& a, hipStream_t st, bool 
     Scope prof(DGRAD ? K_DENSE_DGRAD : K_DENSE_FWD, st, true);
     if (const int nt4 = use_dense4(g, a.resid, lastd)) {
         took(P_DENSE4);
+        if (!DGRAD && cf > 0) took(P_DENSE4_CF);
+        if (nt4 == 2) took(P_DENSE4_NT2);   // dense4_kernel<2>, or the wide part of the dual launch below
         const long groups = g.tiles / 4;
         const long sets = (groups + 3) / 4;
         auto go = [&](auto nt_tag, long set0, long nsets) {
@@ -778,6 +782,7 @@ DenseBlocks launch_dense(const Geo& g, const DenseArgs& a, hipStream_t st, bool 
             return DenseBlocks{2, (long)g.Mp, 1};
         }
         const long main_sets = dense4_main_sets(g, sets, true);
+        took(P_DENSE4_DUAL);   // counted with or without a tail part
         if (main_sets < sets) took(P_DENSE4_TAIL);
         if constexpr (!DGRAD) {
             switch (cf) {

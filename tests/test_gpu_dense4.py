@@ -80,6 +80,11 @@ def test_dense4_matches_dense_kernel(case, mode, monkeypatch):
     L = case[5]
     assert c_old.get("dense4", 0) == 0
     assert c_new["dense4"] == 2 * (L - 1), c_new                     # every hidden-layer GEMM, forward and data gradient
+    nt2_legal = ((case[4] + 31) // 32) % 2 == 0                          # an even number of 32-column tiles
+    if mode == "2" and nt2_legal:
+        assert c_new["dense4_nt2"] == 2 * (L - 1), c_new                 # 64-column blocks for every one of them
+    else:
+        assert c_new["dense4_nt2"] == 0, c_new
     for k in old:
         e = rel_err(new[k], old[k])
         assert e < (1e-5 if case[4] >= 500 else 2e-6), (case[0], k, e)   # H = 500: sums over 6272 rows of differently-rounded logits
@@ -95,6 +100,7 @@ def test_dense4_forward_activations_are_bit_identical(monkeypatch):
     for mode in ("1", "2"):
         new, c_new = _run(case, mode, monkeypatch)
         assert c_new["dense4"] == 2
+        assert c_new["dense4_nt2"] == (2 if mode == "2" else 0), (mode, c_new)
         assert np.array_equal(old["y"], new["y"]) and np.array_equal(old["logits"], new["logits"]), mode
 
 
@@ -124,6 +130,9 @@ def test_split_layer_launch_matches_single_launch(case, monkeypatch):
     assert c_one.get("dense4_tail", 0) == 0
     expect = 2 * (case[5] - 1) if case[6] <= 2 else 2 * (case[5] - 1) - 1      # C = 3: the logits partials have no room for a tail
     assert c_two["dense4_tail"] == expect, c_two
+    # the split and the unsplit wide launch are both dense4_dual_kernel (the latter with an empty tail part)
+    assert c_one["dense4_dual"] == expect and c_two["dense4_dual"] == expect, (c_one, c_two)
+    assert c_one["dense4_nt2"] == 2 * (case[5] - 1) and c_two["dense4_nt2"] == 2 * (case[5] - 1), (c_one, c_two)
     for k in one:
         e = rel_err(two[k], one[k])
         assert e < (1e-5 if case[4] >= 500 else 2e-6), (case[0], k, e)
