@@ -203,13 +203,123 @@ def save_models(path_prefix, epoch_str, p_net, q_net, device=None):
     views into dp.TrainStep's flat buffers, and a Module._apply round trip would re-allocate them -- the optimiser
     would keep stepping the orphaned flat buffer while the forward pass read stale module tensors."""
     for tag, net in (("generator", p_net), ("inference", q_net)):
-        sinks = net.__dict__.pop("_grad_sinks", None)       # views into a training buffer: not part of the model
-        try:
-            snapshot = copy.deepcopy(net).eval().cpu()
-        finally:
-            if sinks is not None:
-                net._grad_sinks = sinks
+        snapshot = copy.deepcopy(net).eval().cpu()      # the classes' __getstate__ leaves the gradient sinks out of the copy
         torch.save(snapshot, "{}_{}_epoch{}.sav".format(path_prefix, tag, epoch_str))
+
+
+# ---- full training checkpoints (--checkpoint_interval / --resume) ---------------------------------------------------------
+CHECKPOINT_VERSION = 1
+
+# Arguments a resumed run may change: where it writes, where it runs, how long it goes on and what it reports.  Every other
+# stored argument shapes the model, the data or the order in which random numbers are consumed (--save_interval too, for mnist
+# and galaxy: a dump epoch draws the display helpers' noise) and must equal the stored value.
+RESUME_FREE_ARGS = {"num_epochs", "save_prefix", "device", "progress_every", "resume", "checkpoint_interval", "no_preload",
+                    "train_path", "test_path", "logging_level"}
+
+
+class CheckpointError(SystemExit):
+    """A state file that cannot be read or does not belong to this run: the command line ends with the message."""
+
+
+def rng_state():
+    """The two host generators all randomness of a run is consumed from, as tensors and numbers (np.random.get_state() is a
+    tuple holding an ndarray: stored as such it would need a full unpickler)."""
+    kind, keys, pos, has_gauss, cached = np.random.get_state()
+    return {"torch": torch.get_rng_state().clone(), "numpy_kind": str(kind),
+            "numpy_keys": torch.from_numpy(np.asarray(keys, np.uint32).astype(np.int64)), "numpy_pos": int(pos),
+            "numpy_has_gauss": int(has_gauss), "numpy_cached_gaussian": float(cached)}
+
+
+def set_rng_state(state):
+    torch.set_rng_state(state["torch"])
+    np.random.set_state((state["numpy_kind"], state["numpy_keys"].numpy().astype(np.uint32), int(state["numpy_pos"]),
+                         int(state["numpy_has_gauss"]), float(state["numpy_cached_gaussian"])))
+
+
+def plain_args(args):
+    """vars(args) with values a weights-only load gives back unchanged."""
+    out = {}
+    for k, v in vars(args).items():
+        out[k] = v if isinstance(v, (bool, int, float, str, type(None))) else str(v)
+    return out
+
+
+def dataset_fingerprint(y_train, y_test):
+    """The float64 sums the loop already forms to check that data-parallel ranks hold one dataset, plus the shapes."""
+    return {"sums": torch.stack([y_train.double().sum(), y_test.double().sum()]).cpu(),
+            "train_shape": [int(d) for d in y_train.shape], "test_shape": [int(d) for d in y_test.shape]}
+
+
+def checkpoint_path(path_prefix, epoch_str):
+    return "{}_state_epoch{}.ckpt".format(path_prefix, epoch_str)
+
+
+def write_checkpoint(path, train_state, completed, args, world, fingerprint, lines):
+    """One torch.save of a dict that torch.load(weights_only=True) reads.  Written under a temporary name in the same
+    directory and renamed over `path`, so an interrupted write never leaves a file with the final name (and never damages the
+    previous one).  Draws no random number: the generator states stored are the caller's states at this moment."""
+    payload = {"version": CHECKPOINT_VERSION, "completed": int(completed), "train_step": train_state, "rng": rng_state(),
+               "args": plain_args(args) if not isinstance(args, dict) else dict(args), "world": int(world),
+               "fingerprint": fingerprint, "lines": {k: list(v) for k, v in lines.items()}}
+    tmp = "{}.tmp{}".format(path, os.getpid())
+    try:
+        torch.save(payload, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return path
+
+
+def read_checkpoint(path):
+    """The dict of write_checkpoint, read with the weights-only unpickler on the CPU.  Anything that is not such a file --
+    missing, truncated, another format -- ends in one CheckpointError naming the path."""
+    try:
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+    except Exception as e:
+        raise CheckpointError("--resume: cannot read the state file {}: {}: {}".format(
+            path, type(e).__name__, str(e).splitlines()[0] if str(e) else "")) from None
+    if not isinstance(ck, dict) or "version" not in ck:
+        raise CheckpointError("--resume: {} is not a training state file (no version field)".format(path))
+    if ck["version"] != CHECKPOINT_VERSION:
+        raise CheckpointError("--resume: {}: format version {} (this build reads version {})".format(
+            path, ck["version"], CHECKPOINT_VERSION))
+    missing = [k for k in ("completed", "train_step", "rng", "args", "world", "fingerprint", "lines") if k not in ck]
+    if missing:
+        raise CheckpointError("--resume: {}: fields missing: {}".format(path, ", ".join(missing)))
+    return ck
+
+
+def check_resume_args(ck, args, script):
+    """Refuse a state file whose run differs from this command line in anything that changes the model or the trajectory, and
+    one that has nothing left to do.  Every rank reads the same file and the same arguments, so all refuse alike."""
+    now = plain_args(args)
+    free = set(RESUME_FREE_ARGS)
+    if script == "particles":
+        free.add("save_interval")           # particles dumps no images: the interval only decides when .sav files are written
+    for k in sorted(set(ck["args"]) | set(now)):
+        if k in free:
+            continue
+        if k not in ck["args"] or k not in now or ck["args"][k] != now[k]:
+            raise CheckpointError("--resume: argument {} is {!r} now but the state file was written with {!r}".format(
+                k, now.get(k, "<absent>"), ck["args"].get(k, "<absent>")))
+    if ck["completed"] >= args.num_epochs:
+        raise CheckpointError("--resume: completed epochs {} >= num_epochs {}: nothing left to run (give a larger "
+                              "num_epochs to extend the run)".format(ck["completed"], args.num_epochs))
+
+
+def check_resume_fingerprint(ck, fingerprint):
+    """The sums are float64 sums of fp32 values: two evaluations over the same data agree to ~1e-16 times sqrt(count) whatever
+    the summation order (host or device, any thread count), two datasets do not.  1e-12 relative separates them."""
+    have = ck["fingerprint"]
+    for k in ("train_shape", "test_shape"):
+        if list(have[k]) != list(fingerprint[k]):
+            raise CheckpointError("--resume: dataset fingerprint differs: {} is {} now, {} in the state file".format(
+                k, fingerprint[k], list(have[k])))
+    a, b = have["sums"].double(), fingerprint["sums"].double()
+    if not bool(((a - b).abs() <= 1e-12 * b.abs().clamp_min(1.0)).all()):
+        raise CheckpointError("--resume: dataset fingerprint differs: sums are {} now, {} in the state file".format(
+            b.tolist(), a.tolist()))
 
 
 def _metric_vector(out):
@@ -305,6 +415,17 @@ def train_main(script, args, build):
     p_net, q_net, rotate, translate, table)."""
     rank, world, local = dp.init_process_group(device_is_gpu=True)
     device = pick_device(args.device, world, local)
+    # --resume: every rank opens the file itself and checks it against its own (identical) arguments before the first
+    # collective, so a rank that cannot read it -- or a run that does not match -- ends here and not inside a broadcast
+    resume = None
+    if getattr(args, "resume", None):
+        resume = read_checkpoint(args.resume)
+        check_resume_args(resume, args, script)
+    ckpt_every = getattr(args, "checkpoint_interval", 0) or 0
+    if ckpt_every < 0:
+        raise SystemExit("the checkpoint interval must be >= 0")
+    if ckpt_every and script == "particles" and args.save_prefix is None:
+        raise SystemExit("--checkpoint-interval needs --save-prefix (the state files are written beside the .sav files)")
     # Randomness is consumed from torch's GLOBAL CPU generator and np.random in the order the reference's main() consumes
     # them (SURVEY.md A.6): default initialisation of p_net then q_net, one draw for the sample-image pass over the validation
     # loader, then per epoch the two draws of iter(DataLoader(shuffle=True)), one N(0,1) draw per training minibatch, one draw
@@ -337,13 +458,6 @@ def train_main(script, args, build):
             print(p_net, file=f)
             print(q_net, file=f)
     x = coord_grid(cfg["n"], cfg["m"]).to(device)
-    fn = {"mnist": E.eval_minibatch_mnist, "galaxy": E.eval_minibatch_galaxy, "particles": E.eval_minibatch_particles}[script]
-    step = dp.TrainStep(p_net, q_net, fn, lr=args.learning_rate, rotate=cfg["rotate"], translate=cfg["translate"],
-                        dx_scale=args.dx_scale, theta_prior=args.theta_prior)
-    print("# using priors: theta={}, dx={}".format(args.theta_prior, args.dx_scale), file=sys.stderr)
-    num_epochs = args.num_epochs
-    digits = int(math.log10(num_epochs)) + 1
-    bs = args.minibatch_size
     # the dataset is resident in HBM (the reference preloads it too: train_mnist.py:329-332) unless --no-preload
     # (train_particles.py:317, :405-413) keeps it in host memory, from where each minibatch is gathered and uploaded
     home = torch.device("cpu") if getattr(args, "no_preload", False) else device
@@ -352,6 +466,18 @@ def train_main(script, args, build):
     mask = cfg.get("mask")
     mask = mask.to(device) if mask is not None else None
     N = tr["y"].size(0)
+    fingerprint = None
+    if resume is not None or ckpt_every:
+        fingerprint = dataset_fingerprint(tr["y"], te["y"])
+        if resume is not None:
+            check_resume_fingerprint(resume, fingerprint)
+    fn = {"mnist": E.eval_minibatch_mnist, "galaxy": E.eval_minibatch_galaxy, "particles": E.eval_minibatch_particles}[script]
+    step = dp.TrainStep(p_net, q_net, fn, lr=args.learning_rate, rotate=cfg["rotate"], translate=cfg["translate"],
+                        dx_scale=args.dx_scale, theta_prior=args.theta_prior)
+    print("# using priors: theta={}, dx={}".format(args.theta_prior, args.dx_scale), file=sys.stderr)
+    num_epochs = args.num_epochs
+    digits = int(math.log10(num_epochs)) + 1
+    bs = args.minibatch_size
     if world > 1:       # every rank must hold the SAME dataset: the ranks slice one global minibatch by index
         dp.assert_same_on_all_ranks(torch.stack([tr["y"].double().sum(), te["y"].double().sum()]).to(device), "the dataset")
     inf_dim = q_net.latent_dim
@@ -367,7 +493,26 @@ def train_main(script, args, build):
         loader_order(ntest, False)                                   # validation loader (train_mnist.py:402) -> one draw
         if out_dir:
             export_batch_as_image(te["y"][:bs], "{}/images/_sample_{}.png".format(out_dir, label), [cfg["n"], cfg["m"]])
-    for epoch in range(num_epochs):
+    first_epoch = 0
+    rows = []                                                        # particles: the table rows printed so far
+    if resume is not None:
+        # the networks were built and the pre-loop draws made exactly as a fresh run makes them; now the trained state
+        # replaces the initial one and -- last, immediately before the first resumed epoch -- the two generators continue
+        # where the stored run's were after its last evaluation pass
+        step.load_state_dict(resume["train_step"])
+        first_epoch = int(resume["completed"])
+        stored = resume["lines"]
+        train_lines = list(stored.get("train_lines", train_lines))
+        val_lines = list(stored.get("val_lines", val_lines))
+        rows = list(stored.get("rows", rows))
+        if rank == 0:
+            print("# resuming {} after epoch {} of {} (written under {} rank(s), now {})".format(
+                args.resume, first_epoch, num_epochs, resume["world"], world), file=sys.stderr)
+        set_rng_state(resume["rng"])
+    state_prefix = None
+    if ckpt_every and rank == 0:
+        state_prefix = prefix if script == "particles" else os.path.join(trained, prefix)
+    for epoch in range(first_epoch, num_epochs):
         kw = {}
         if script != "mnist":
             kw["z_scale"] = 0 if epoch < z_delay else 1
@@ -391,8 +536,10 @@ def train_main(script, args, build):
                        dict(data=te, mask=mask, kw=kw, dump=dump, inf_dim=inf_dim, noise=noise))
         if rank == 0:
             if script == "particles":
-                print("\t".join([str(epoch + 1), "train", str(e), str(g), str(k)]), file=out)
-                print("\t".join([str(epoch + 1), "test", str(ev[0]), str(ev[1]), str(ev[2])]), file=out)
+                rows.append("\t".join([str(epoch + 1), "train", str(e), str(g), str(k)]))
+                rows.append("\t".join([str(epoch + 1), "test", str(ev[0]), str(ev[1]), str(ev[2])]))
+                print(rows[-2], file=out)
+                print(rows[-1], file=out)
             else:
                 line = "\t".join(map(str, [epoch, e, g, k]))
                 train_lines.append(line)
@@ -403,6 +550,9 @@ def train_main(script, args, build):
             out.flush()
             if script == "particles" and prefix is not None and (epoch + 1) % args.save_interval == 0:
                 save_models(prefix, str(epoch + 1).zfill(digits), p_net, q_net, device)
+            if state_prefix is not None and ((epoch + 1) % ckpt_every == 0 or epoch + 1 == num_epochs):
+                write_checkpoint(checkpoint_path(state_prefix, str(epoch + 1).zfill(digits)), step.state_dict(), epoch + 1,
+                                 args, world, fingerprint, dict(train_lines=train_lines, val_lines=val_lines, rows=rows))
     if rank == 0 and script != "particles":
         save_models(os.path.join(trained, prefix), str(num_epochs).zfill(digits), p_net, q_net, device)
         with open(os.path.join(out_dir, "train.txt"), "w") as f:

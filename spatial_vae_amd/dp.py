@@ -391,9 +391,116 @@ class TrainStep(object):
         self.sync_replicas()
 
     def sync_replicas(self):
-        """Make every replica rank 0's: each process initialised its modules from its own RNG."""
-        if collectives_on():
-            dist.broadcast(self.grads.flat_param, src=0)
+        """Make every replica rank 0's: each process initialised its modules from its own RNG.  Once the optimiser holds
+        state (after load_state_dict) both moments and the step count go out too, so the replicas are bit-equal whatever each
+        rank read."""
+        if not collectives_on():
+            return
+        dist.broadcast(self.grads.flat_param, src=0)
+        st = self.optim.state.get(self.master)
+        if st:
+            dist.broadcast(st["exp_avg"], src=0)
+            dist.broadcast(st["exp_avg_sq"], src=0)
+            count = torch.tensor([int(st["step"])], dtype=torch.int64, device=self.device)
+            dist.broadcast(count, src=0)
+            self._set_step_count(st, int(count.item()))
+
+    # ---- training state (checkpoints) ---------------------------------------------------------------
+    STATE_VERSION = 1
+
+    def _named_tensors(self):
+        """[(net key, state-dict name, tensor, offset in the flat buffers or None)] of both modules, in state-dict order."""
+        offset = {id(p): off for p, off in zip(self.grads.params, self.grads.offsets)}
+        out = []
+        for key, net in (("p_net", self.p_net), ("q_net", self.q_net)):
+            params = dict(net.named_parameters())
+            for name, t in net.state_dict(keep_vars=True).items():
+                out.append((key, name, t, offset.get(id(params.get(name)))))
+        return out
+
+    @staticmethod
+    def _set_step_count(st, count):
+        if torch.is_tensor(st["step"]):
+            st["step"].fill_(count)             # torch.optim.Adam keeps a tensor
+        else:
+            st["step"] = int(count)             # ops.FlatAdam a Python int
+
+    def _adam_state(self):
+        """The optimiser's state for the flat master, created (zero moments, step 0) the way the optimiser's first step would
+        create it if no step has run yet in this process."""
+        st = self.optim.state[self.master]
+        if not st:
+            group = self.optim.param_groups[0]
+            if isinstance(self.optim, torch.optim.Adam):
+                on_device = bool(group.get("capturable") or group.get("fused"))
+                st["step"] = torch.zeros((), dtype=torch.float32, device=self.master.device if on_device else "cpu")
+            else:
+                st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(self.master, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(self.master, memory_format=torch.preserve_format)
+        return st
+
+    def state_dict(self):
+        """Everything the next step depends on, as plain CPU tensors and Python scalars: the two modules' state-dicts and
+        Adam's moments cut into the same per-parameter names (so a file does not depend on the flat layout), the step count
+        and the hyper-parameters.  One copy-out of each of the three flat buffers (the per-name tensors are views of those host
+        copies); nothing on the device moves and no random number is drawn."""
+        group = self.optim.param_groups[0]
+        st = self.optim.state.get(self.master) or {}
+        host = {"param": self.grads.flat_param.detach().cpu()}
+        for k in ("exp_avg", "exp_avg_sq"):
+            host[k] = st[k].detach().cpu() if k in st else torch.zeros_like(host["param"])
+        out = {"version": self.STATE_VERSION, "step": int(st.get("step", 0)), "lr": float(group["lr"]),
+               "betas": [float(b) for b in group["betas"]], "eps": float(group["eps"]),
+               "p_net": {}, "q_net": {}, "exp_avg": {"p_net": {}, "q_net": {}}, "exp_avg_sq": {"p_net": {}, "q_net": {}}}
+        for key, name, t, off in self._named_tensors():
+            if off is None:                                 # a buffer or a frozen parameter: not in the flat buffers, no moments
+                out[key][name] = t.detach().cpu().clone()
+                continue
+            out[key][name] = host["param"][off:off + t.numel()].view(t.shape)
+            for k in ("exp_avg", "exp_avg_sq"):
+                out[k][key][name] = host[k][off:off + t.numel()].view(t.shape)
+        return out
+
+    def load_state_dict(self, state):
+        """Copy a state_dict() INTO the existing flat buffers: no parameter and no moment is rebound, so the modules stay
+        views of the flat parameter buffer, the gradient sinks keep pointing into grads.flat and the alignment padding is not
+        touched.  The optimiser's state is created first if no step has run yet.  Names, shapes and dtypes must match.  Under
+        data parallel execution every rank loads, then rank 0's parameters and moments are broadcast."""
+        if state.get("version") != self.STATE_VERSION:
+            raise ValueError("TrainStep.load_state_dict: version %r, this build reads version %d"
+                             % (state.get("version"), self.STATE_VERSION))
+        mine = self._named_tensors()
+        for key in ("p_net", "q_net"):
+            have = {name for k, name, _, _ in mine if k == key}
+            missing, extra = sorted(have - set(state[key])), sorted(set(state[key]) - have)
+            if missing or extra:
+                raise KeyError("TrainStep.load_state_dict: %s: missing %s, unexpected %s" % (key, missing, extra))
+        plan = []
+        for key, name, t, off in mine:
+            srcs = [("", state[key][name])]
+            if off is not None:
+                for k in ("exp_avg", "exp_avg_sq"):
+                    if name not in state[k][key]:
+                        raise KeyError("TrainStep.load_state_dict: %s.%s: missing %s" % (key, name, k))
+                    srcs.append((k, state[k][key][name]))
+            for k, src in srcs:
+                if not torch.is_tensor(src) or tuple(src.shape) != tuple(t.shape) or src.dtype != t.dtype:
+                    raise ValueError("TrainStep.load_state_dict: %s.%s%s: expected %s %s, got %s %s"
+                                     % (key, name, " (" + k + ")" if k else "", tuple(t.shape), t.dtype,
+                                        tuple(src.shape) if torch.is_tensor(src) else type(src).__name__,
+                                        getattr(src, "dtype", "")))
+            plan.append((t, off, srcs))
+        st = self._adam_state()
+        with torch.no_grad():
+            for t, off, srcs in plan:
+                t.detach().copy_(srcs[0][1])
+                for k, src in srcs[1:]:
+                    st[k][off:off + t.numel()].view(t.shape).copy_(src)
+        self._set_step_count(st, int(state["step"]))
+        group = self.optim.param_groups[0]
+        group["lr"], group["betas"], group["eps"] = float(state["lr"]), tuple(float(b) for b in state["betas"]), float(state["eps"])
+        self.sync_replicas()
 
     def aliased(self):
         """True while every module parameter still lives inside the flat parameter buffer (a Module._apply round trip --

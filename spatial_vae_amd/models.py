@@ -13,6 +13,8 @@ import torch.nn.functional as F
 
 from . import ops
 
+__all__ = ["ResidLinear", "InferenceNetwork", "SpatialGenerator", "VanillaGenerator"]
+
 _ACT_NAMES = {nn.Tanh: "tanh", nn.LeakyReLU: "leakyrelu", nn.ReLU: "relu", nn.Sigmoid: "sigmoid"}
 
 
@@ -24,7 +26,20 @@ def _act_name(activation):
                                   % (sorted(a.__name__ for a in _ACT_NAMES), activation))
 
 
-class ResidLinear(nn.Module):
+_NOT_PICKLED = ("_spec", "_grad_sinks")
+
+
+class _ReferencePickle(object):
+    """Whole-module pickles (torch.save(net): the only checkpoint the reference's scripts write, src/misc_tools.py:88-104)
+    carry the reference's attribute set and nothing else: the kernel description `_spec` is derived again on load, and the
+    gradient sinks dp.TrainStep hangs on a module are views into a training buffer, not part of the model.  copy.deepcopy
+    goes through the same pair, so a copy never aliases the flat gradient buffer either."""
+
+    def __getstate__(self):
+        return {k: v for k, v in self.__dict__.items() if k not in _NOT_PICKLED}
+
+
+class ResidLinear(_ReferencePickle, nn.Module):
     """act(linear(x) + x)."""
 
     def __init__(self, n_in, n_out, activation=nn.Tanh):
@@ -49,7 +64,7 @@ def _mlp_trunk(n_in, hidden_dim, num_layers, activation, resid, first_is_linear)
     return mods
 
 
-class InferenceNetwork(nn.Module):
+class InferenceNetwork(_ReferencePickle, nn.Module):
     """Encoder MLP; returns (z_mu, z_logstd), the two halves of the last layer's output."""
 
     def __init__(self, n, latent_dim, hidden_dim, num_layers=1, activation=nn.Tanh, resid=False):
@@ -66,7 +81,7 @@ class InferenceNetwork(nn.Module):
         return out[:, :self.latent_dim], out[:, self.latent_dim:]
 
 
-class SpatialGenerator(nn.Module):
+class SpatialGenerator(_ReferencePickle, nn.Module):
     """Coordinate-conditioned MLP decoder; forward runs in the HIP library."""
 
     def __init__(self, latent_dim, hidden_dim, n_out=1, num_layers=1, activation=nn.Tanh,
@@ -88,10 +103,28 @@ class SpatialGenerator(nn.Module):
                                      act=_act_name(activation), softplus=bool(softplus), resid=bool(resid),
                                      expand_coords=bool(expand_coords),
                                      bilinear=bool(bilinear) and latent_dim > 0)
-        slope = [m.negative_slope for m in self.layers if isinstance(m, nn.LeakyReLU)]
+        self._check_slopes()
+        print(self)
+
+    def _check_slopes(self):
+        slope = [m.negative_slope for m in self.layers.modules() if isinstance(m, nn.LeakyReLU)]
         if any(s != 0.01 for s in slope):
             raise NotImplementedError("LeakyReLU slope other than the default 0.01")
-        print(self)
+
+    def __setstate__(self, state):
+        """A pickled module holds the reference's attributes only (it may have been written by the reference itself): the
+        kernel description is read off what the module holds, and what the kernels cannot run is refused here, with the
+        constructor's message, not at the first forward."""
+        super().__setstate__(state)
+        if "_spec" not in self.__dict__:
+            hidden_lin, out_lin = self._linears()
+            self._spec = ops.DecoderSpec(latent_dim=self.latent_dim, hidden_dim=self.coord_linear.out_features,
+                                         n_out=out_lin.out_features, num_layers=len(hidden_lin) + 1,
+                                         act=_act_name(type(self.layers[0])), softplus=bool(self.softplus),
+                                         resid=any(isinstance(m, ResidLinear) for m in self.layers),
+                                         expand_coords=self.coord_linear.in_features == 5,
+                                         bilinear=hasattr(self, "bilinear"))
+            self._check_slopes()
 
     # -- parameter plumbing ---------------------------------------------------------------
     def _linears(self):
@@ -151,7 +184,7 @@ class SpatialGenerator(nn.Module):
         return out if return_logits else out[0]
 
 
-class VanillaGenerator(nn.Module):
+class VanillaGenerator(_ReferencePickle, nn.Module):
     """Plain MLP decoder z -> all pixels (the --vanilla baseline); ordinary PyTorch."""
 
     def __init__(self, n, latent_dim, hidden_dim, n_out=1, num_layers=1, activation=nn.Tanh,
@@ -171,3 +204,11 @@ class VanillaGenerator(nn.Module):
         if self.softplus:
             y = torch.cat([F.softplus(y[:, :, :1]), y[:, :, 1:]], 2)
         return y
+
+
+# The classes pickle under the reference's class path, so a whole-module .sav written here opens where only the reference's
+# spatial_vae.models exists, and one written there opens here (spatial_vae/models.py re-exports these very objects).  Files of
+# earlier builds name spatial_vae_amd.models, which still resolves to the same classes.
+for _cls in (ResidLinear, InferenceNetwork, SpatialGenerator, VanillaGenerator):
+    _cls.__module__ = "spatial_vae.models"
+del _cls

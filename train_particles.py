@@ -54,6 +54,13 @@ def particle_arguments(argv=None):
                    help="seed torch and numpy before the networks are built (the reference has no such flag: unseeded by default)")
     p.add_argument("--gemm", choices=["fp32", "fp16x3"], default=None,
                    help="hidden-layer GEMM path (default: SVAE_GEMM or fp32 MFMA; fp16x3 = fp32-accurate split-operand f16 MFMA)")
+    p.add_argument("--resume", default=None, metavar="PATH",
+                   help="continue from this training state file (written by --checkpoint-interval) with the same arguments; only --num-epochs "
+                        "may grow.  Under the world size that wrote it the run continues bit for bit; another world size is "
+                        "accepted but changes the summation order, as it does for a fresh run")
+    p.add_argument("--checkpoint-interval", type=int, default=0, metavar="N",
+                   help="write <prefix>_state_epoch<NN>.ckpt (parameters, Adam moments, step count, generator states, table rows) "
+                        "beside the .sav files after every N-th epoch and after the last one (0 = never)")
     return p.parse_args(argv)
 
 
