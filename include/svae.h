@@ -256,6 +256,60 @@ int svae_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
                    float beta2, float eps, int64_t step, int32_t zero_grad, svae_stream_t stream);
 
 /*
+ * Gradient guard: global-norm clipping and "skip the update when the gradient is not finite", decided and applied on
+ * the device.  The reference has neither (loss = -elbo; backward; optim.step(), train_mnist.py:147-149: one non-finite
+ * gradient goes straight into both Adam moments); the host-side spelling would be
+ *     total = torch.nn.utils.clip_grad_norm_(params, max_norm)
+ *     if torch.isfinite(total): optim.step()
+ * which reads the device inside every step.  Here the decision lives in a small control record in device memory, written
+ * by svae_grad_guard_norm and read by svae_adam_step_guarded; the host never sees it unless it copies it out.
+ * Layout: ALL ZERO BYTES = a fresh record (step count 0, empty statistics).  `t` is Adam's step count (the number of
+ * updates applied); the statistics run since the caller last zeroed them (the bytes from `steps` to the end).
+ */
+typedef struct svae_guard_control {
+    int64_t t;        /* updates applied so far; advanced by svae_grad_guard_norm when the norm is finite */
+    float total;      /* this step's (= the last) global L2 norm */
+    float coef;       /* min(1, max_norm / (total + 1e-6)): what the gradient is scaled by */
+    float step_size;  /* lr / (1 - beta1^t) */
+    float sqrt_bc2;   /* sqrt(1 - beta2^t) */
+    int32_t apply;    /* 1 = update, 0 = leave parameters and moments alone */
+    int32_t finite;   /* isfinite(total) */
+    int64_t steps;    /* statistics: calls seen, */
+    int64_t clipped;  /*   of those applied with coef < 1, */
+    int64_t skipped;  /*   of those not applied, */
+    double norm_sum;  /*   sum of the finite norms, */
+    float norm_max;   /*   largest finite norm */
+    float reserved;
+} svae_guard_control;
+
+/* sizeof(svae_guard_control): what the caller allocates (8-byte aligned) and zeroes once. */
+size_t svae_grad_guard_control_bytes(void);
+
+/* Scratch svae_grad_guard_norm needs for a buffer of n floats (one double per chunk; 0 = invalid n). */
+size_t svae_grad_guard_workspace_bytes(int64_t n);
+
+/*
+ * Replaces total = clip_grad_norm_(params, max_norm) and the `if isfinite(total)` decision around optim.step() (see
+ * above; the reference has neither).  Two launches: the sum of squares of grad[0..n) per contiguous chunk, accumulated in
+ * double (values above 1.8e19 do not overflow) in a fixed order that depends on n only -- the same buffer gives the same
+ * bits on any device --, then one workgroup that sums the chunks in index order and writes `control`:
+ * total = (float)sqrt(sum); finite = isfinite(total); coef = min(1, max_norm / (total + 1e-6f)) in fp32 (max_norm = +inf:
+ * 1); if finite, t += 1, step_size and sqrt_bc2 for the new t (formed in double, rounded to float) and apply = 1, else
+ * apply = 0 and t unchanged; and the statistics.  grad must be 16-byte aligned, ws 256-byte aligned, max_norm > 0.
+ */
+int svae_grad_guard_norm(const float* grad, int64_t n, float max_norm, float lr, float beta1, float beta2,
+                         svae_guard_control* control, void* ws, size_t ws_bytes, svae_stream_t stream);
+
+/*
+ * Replaces optim.step() under that guard: svae_adam_step with grad * control->coef formed on load (no scaling pass),
+ * lr / (1 - beta1^t) and sqrt(1 - beta2^t) taken from `control`, and nothing written to param, exp_avg or exp_avg_sq when
+ * control->apply == 0.  zero_grad != 0 clears `grad` behind it in both cases.
+ */
+int svae_adam_step_guarded(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
+                           float beta2, float eps, int32_t zero_grad, const svae_guard_control* control,
+                           svae_stream_t stream);
+
+/*
  * Rotation augmentation of the observed images before inference: the reference rotates each image of the
  * minibatch by its own random angle with Pillow, one image at a time on the host (train_galaxy.py:41-54: uint8
  * images, `im.rotate(360*offset/2/pi, resample=Image.BICUBIC)`; train_particles.py:31-43: float32 images).  This is

@@ -18,10 +18,11 @@ ABI_VERSION = 2
 
 # every function include/svae.h declares; build() and tests/test_host_cpu.py re-derive this list from the header and check it
 # against the library's exports (the header is documentation: importing the package must not need it)
-EXPORTS = ("svae_abi_version", "svae_adam_step", "svae_bce_loglik", "svae_colsum", "svae_ctf_filter",
+EXPORTS = ("svae_abi_version", "svae_adam_step", "svae_adam_step_guarded", "svae_bce_loglik", "svae_colsum", "svae_ctf_filter",
            "svae_ctf_filter_workspace_bytes", "svae_decoder_backward", "svae_decoder_forward",
            "svae_decoder_forward_bce", "svae_elbo_head_backward", "svae_elbo_head_forward", "svae_gaussian_loglik",
-           "svae_gaussian_workspace_bytes", "svae_gemm_mode_get", "svae_gemm_mode_set", "svae_last_error",
+           "svae_gaussian_workspace_bytes", "svae_gemm_mode_get", "svae_gemm_mode_set", "svae_grad_guard_control_bytes",
+           "svae_grad_guard_norm", "svae_grad_guard_workspace_bytes", "svae_last_error",
            "svae_latent_backward", "svae_latent_forward", "svae_linear_backward", "svae_linear_forward",
            "svae_path_counts", "svae_path_name", "svae_profile_enable", "svae_profile_kind_name",
            "svae_profile_read", "svae_rotate_bicubic", "svae_saved_bytes", "svae_workspace_bytes")
@@ -57,6 +58,14 @@ class LatentDesc(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("inf_dim", ctypes.c_int32), ("rotate", ctypes.c_int32),
                 ("translate", ctypes.c_int32), ("mu_penalty", ctypes.c_int32), ("dx_scale", ctypes.c_float),
                 ("z_scale", ctypes.c_float), ("theta_prior", ctypes.c_float)]
+
+
+class GuardControl(ctypes.Structure):
+    """svae_guard_control: all zero bytes = a fresh record; the statistics are the bytes from `steps` to the end."""
+    _fields_ = [("t", ctypes.c_int64), ("total", ctypes.c_float), ("coef", ctypes.c_float), ("step_size", ctypes.c_float),
+                ("sqrt_bc2", ctypes.c_float), ("apply", ctypes.c_int32), ("finite", ctypes.c_int32), ("steps", ctypes.c_int64),
+                ("clipped", ctypes.c_int64), ("skipped", ctypes.c_int64), ("norm_sum", ctypes.c_double),
+                ("norm_max", ctypes.c_float), ("reserved", ctypes.c_float)]
 
 
 class PoseGrads(ctypes.Structure):
@@ -116,6 +125,16 @@ def lib():
     L.svae_adam_step.restype = ctypes.c_int
     L.svae_adam_step.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, ctypes.c_int64, i32, vp]
+    L.svae_grad_guard_control_bytes.restype = sz
+    L.svae_grad_guard_control_bytes.argtypes = []
+    L.svae_grad_guard_workspace_bytes.restype = sz
+    L.svae_grad_guard_workspace_bytes.argtypes = [ctypes.c_int64]
+    L.svae_grad_guard_norm.restype = ctypes.c_int
+    L.svae_grad_guard_norm.argtypes = [vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                       vp, vp, sz, vp]
+    L.svae_adam_step_guarded.restype = ctypes.c_int
+    L.svae_adam_step_guarded.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, i32,
+                                         vp, vp]
     L.svae_rotate_bicubic.restype = ctypes.c_int
     L.svae_rotate_bicubic.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     L.svae_ctf_filter.restype = ctypes.c_int
@@ -138,6 +157,9 @@ def lib():
     if L.svae_abi_version() != ABI_VERSION:
         raise RuntimeError("spatial_vae_amd: %s has ABI version %d, this binding needs %d -- rebuild it"
                            % (path, L.svae_abi_version(), ABI_VERSION))
+    if L.svae_grad_guard_control_bytes() != ctypes.sizeof(GuardControl):
+        raise RuntimeError("spatial_vae_amd: %s lays out svae_guard_control in %d bytes, this binding in %d -- rebuild it"
+                           % (path, L.svae_grad_guard_control_bytes(), ctypes.sizeof(GuardControl)))
     _lib = L
     return L
 

@@ -215,6 +215,8 @@ CHECKPOINT_VERSION = 1
 # and galaxy: a dump epoch draws the display helpers' noise) and must equal the stored value.
 RESUME_FREE_ARGS = {"num_epochs", "save_prefix", "device", "progress_every", "resume", "checkpoint_interval", "no_preload",
                     "train_path", "test_path", "logging_level"}
+# Arguments added after state files were first written, with the value that reproduces the run of a file that lacks them.
+RESUME_ARG_DEFAULTS = {"clip_grad_norm": None, "skip_nonfinite": False}
 
 
 class CheckpointError(SystemExit):
@@ -297,12 +299,14 @@ def check_resume_args(ck, args, script):
     free = set(RESUME_FREE_ARGS)
     if script == "particles":
         free.add("save_interval")           # particles dumps no images: the interval only decides when .sav files are written
-    for k in sorted(set(ck["args"]) | set(now)):
+    stored = dict(RESUME_ARG_DEFAULTS, **ck["args"])     # a file written before the gradient guard existed: both options off
+    now = dict(RESUME_ARG_DEFAULTS, **now)
+    for k in sorted(set(stored) | set(now)):
         if k in free:
             continue
-        if k not in ck["args"] or k not in now or ck["args"][k] != now[k]:
+        if k not in stored or k not in now or stored[k] != now[k]:
             raise CheckpointError("--resume: argument {} is {!r} now but the state file was written with {!r}".format(
-                k, now.get(k, "<absent>"), ck["args"].get(k, "<absent>")))
+                k, now.get(k, "<absent>"), stored.get(k, "<absent>")))
     if ck["completed"] >= args.num_epochs:
         raise CheckpointError("--resume: completed epochs {} >= num_epochs {}: nothing left to run (give a larger "
                               "num_epochs to extend the run)".format(ck["completed"], args.num_epochs))
@@ -426,6 +430,10 @@ def train_main(script, args, build):
         raise SystemExit("the checkpoint interval must be >= 0")
     if ckpt_every and script == "particles" and args.save_prefix is None:
         raise SystemExit("--checkpoint-interval needs --save-prefix (the state files are written beside the .sav files)")
+    clip = getattr(args, "clip_grad_norm", None)
+    skip_nonfinite = bool(getattr(args, "skip_nonfinite", False))
+    if clip is not None and not clip > 0:
+        raise SystemExit("the gradient-norm threshold must be > 0")
     # Randomness is consumed from torch's GLOBAL CPU generator and np.random in the order the reference's main() consumes
     # them: default initialisation of p_net then q_net, one draw for the sample-image pass over the validation
     # loader, then per epoch the two draws of iter(DataLoader(shuffle=True)), one N(0,1) draw per training minibatch, one draw
@@ -473,7 +481,7 @@ def train_main(script, args, build):
             check_resume_fingerprint(resume, fingerprint)
     fn = {"mnist": E.eval_minibatch_mnist, "galaxy": E.eval_minibatch_galaxy, "particles": E.eval_minibatch_particles}[script]
     step = dp.TrainStep(p_net, q_net, fn, lr=args.learning_rate, rotate=cfg["rotate"], translate=cfg["translate"],
-                        dx_scale=args.dx_scale, theta_prior=args.theta_prior)
+                        dx_scale=args.dx_scale, theta_prior=args.theta_prior, clip_grad_norm=clip, skip_nonfinite=skip_nonfinite)
     print("# using priors: theta={}, dx={}".format(args.theta_prior, args.dx_scale), file=sys.stderr)
     num_epochs = args.num_epochs
     digits = int(math.log10(num_epochs)) + 1
@@ -524,6 +532,11 @@ def train_main(script, args, build):
         if rank == 0:       # run_epoch's values() synchronised: the epoch's training pass is complete
             print("# epoch {}: {} training images in {:.3f} s = {:.0f} images/s".format(
                 epoch + 1, N, time.time() - t_epoch, N / max(time.time() - t_epoch, 1e-9)), file=sys.stderr)
+        if step.guarded:    # every rank clears its (identical) record; the pass has just synchronised for its row
+            gs = step.guard_stats(reset=True)
+            if rank == 0:
+                print("# grad norm: mean {:.6g} max {:.6g} clipped {}/{} skipped {}".format(
+                    gs["mean_norm"], gs["max_norm"], gs["clipped"], gs["steps"], gs["skipped"]), file=sys.stderr)
         dump = None
         shapes = None
         if script != "particles" and (epoch + 1) % args.save_interval == 0:

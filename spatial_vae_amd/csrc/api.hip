@@ -314,10 +314,11 @@ int check_ws(const Plan& p, const void* ws, size_t ws_bytes) {
 
 // ---- opt-in per-kernel timing with HIP events (svae_profile_*)
 enum Kind { K_PREPARE = 0, K_LAYER0_FWD, K_DENSE_FWD, K_OUT_FWD, K_DLOGITS, K_OUT_BWD, K_WGRAD, K_WGRAD_REDUCE,
-            K_DENSE_DGRAD, K_LAYER0_BWD, K_SMALL_BWD, K_BCE, K_GAUSSIAN, K_LATENT, K_ADAM, K_AUGMENT, K_ENCODER, K_COUNT };
+            K_DENSE_DGRAD, K_LAYER0_BWD, K_SMALL_BWD, K_BCE, K_GAUSSIAN, K_LATENT, K_ADAM, K_AUGMENT, K_ENCODER, K_GRAD_NORM,
+            K_ADAM_GUARDED, K_COUNT };
 const char* const kKindNames[SVAE_PROF_KINDS] = {"prepare", "layer0_fwd", "dense_fwd", "out_fwd", "dlogits", "out_bwd",
                                                  "wgrad", "wgrad_reduce", "dense_dgrad", "layer0_bwd", "small_bwd", "bce",
-                                                 "gaussian", "latent", "adam", "augment", "encoder", "", "", ""};
+                                                 "gaussian", "latent", "adam", "augment", "encoder", "grad_norm", "adam_guarded", ""};
 static_assert(K_COUNT <= SVAE_PROF_KINDS, "svae_profile_read arrays too small");
 // which kernel family a call actually dispatched (svae_path_counts): the GEMM mode is a request, the plan decides per
 // geometry (fp16x3 falls back to the fp32 kernels for unbounded activations and odd tile counts), and a test must be able
@@ -1436,6 +1437,52 @@ int svae_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq,
     hipLaunchKernelGGL(adam_kernel, dim3(blocks_for((n + 3) / 4)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, (long)n,
                        (float)(lr / bc1), (float)sqrt(bc2), beta1, beta2, eps, zero_grad ? 1 : 0);
     return launch_status("svae_adam_step");
+}
+
+size_t svae_grad_guard_control_bytes(void) { return sizeof(svae_guard_control); }
+
+size_t svae_grad_guard_workspace_bytes(int64_t n) {
+    if (n < 1 || n > (int64_t(1) << 40)) {
+        fail(SVAE_E_INVALID, "svae_grad_guard_workspace_bytes: bad n");
+        return 0;
+    }
+    const long chunk = grad_norm_chunk((long)n);
+    return (size_t)(((long)n + chunk - 1) / chunk) * sizeof(double);
+}
+
+int svae_grad_guard_norm(const float* grad, int64_t n, float max_norm, float lr, float beta1, float beta2,
+                         svae_guard_control* control, void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (!grad || !control || n < 1 || n > (int64_t(1) << 40)) return fail(SVAE_E_INVALID, "svae_grad_guard_norm: bad arguments");
+    if (!(max_norm > 0.0f)) return fail(SVAE_E_INVALID, "svae_grad_guard_norm: max_norm must be > 0 (+inf = no clipping)");
+    if ((reinterpret_cast<uintptr_t>(grad) & 15) || (reinterpret_cast<uintptr_t>(control) & 7))
+        return fail(SVAE_E_INVALID, "svae_grad_guard_norm: grad must be 16-byte and control 8-byte aligned");
+    const long chunk = grad_norm_chunk((long)n);
+    const long nparts = ((long)n + chunk - 1) / chunk;
+    if (!ws) return fail(SVAE_E_WORKSPACE, "null workspace");
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(SVAE_E_WORKSPACE, "workspace not 256-byte aligned");
+    if (ws_bytes < (size_t)nparts * sizeof(double))
+        return fail(SVAE_E_WORKSPACE, "workspace too small: %zu < %zu", ws_bytes, (size_t)nparts * sizeof(double));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* partial = static_cast<double*>(ws);
+    Scope prof(K_GRAD_NORM, st);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nparts), dim3(256), 0, st, grad, (long)n, chunk, partial);
+    hipLaunchKernelGGL(grad_guard_control_kernel, dim3(1), dim3(256), 0, st, partial, (int)nparts, max_norm, lr, beta1, beta2, control);
+    return launch_status("svae_grad_guard_norm");
+}
+
+int svae_adam_step_guarded(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float beta1,
+                           float beta2, float eps, int32_t zero_grad, const svae_guard_control* control,
+                           svae_stream_t stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !control || n < 1)
+        return fail(SVAE_E_INVALID, "svae_adam_step_guarded: bad arguments");
+    if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+         reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
+        return fail(SVAE_E_INVALID, "svae_adam_step_guarded: buffers must be 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_ADAM_GUARDED, st);
+    hipLaunchKernelGGL(adam_guarded_kernel, dim3(blocks_for((n + 3) / 4)), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq,
+                       (long)n, beta1, beta2, eps, zero_grad ? 1 : 0, control);
+    return launch_status("svae_adam_step_guarded");
 }
 
 int svae_rotate_bicubic(const float* y, float* y_rot, const double* matrix, const int32_t* quarter, int32_t B, int32_t rows,

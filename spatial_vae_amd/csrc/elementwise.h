@@ -1240,4 +1240,131 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
     }
 }
 
+// ---------------------------------------------------------------- gradient guard over the flat buffer (A7: what the reference
+// lacks around optim.step() -- clip_grad_norm_ and "skip the update when the gradient is not finite"), all on the device
+constexpr long kNormChunkMin = 4096;    // floats: 16 KB per workgroup
+constexpr long kNormMaxChunks = 4096;   // the chunk doubles until the buffer is at most this many chunks
+
+// Floats per workgroup of grad_sumsq_kernel.  A function of n ONLY -- not of the device, the CU count or the environment -- so
+// that one buffer gives one bit pattern on every box (the value scales the update, and resume is specified bit for bit).
+__host__ __device__ inline long grad_norm_chunk(long n) {
+    long c = kNormChunkMin;
+    while ((n + c - 1) / c > kNormMaxChunks) c *= 2;
+    return c;
+}
+
+__device__ __forceinline__ double sumsq4(double acc, const float4 a) {
+    // a float's square is exact in double (24 + 24 <= 53 bits): each term costs one rounding, that of the addition
+    acc += (double)a.x * (double)a.x;
+    acc += (double)a.y * (double)a.y;
+    acc += (double)a.z * (double)a.z;
+    acc += (double)a.w * (double)a.w;
+    return acc;
+}
+
+// Stage 1: partial[block] = sum of squares of the block's contiguous chunk of g[0..n), in double (squares of values above
+// 1.8e19 overflow fp32; the pass is HBM-bound, the fp64 adds ride along).  16-byte loads, four in flight per lane; the n % 4
+// scalar tail falls into the last chunk (the chunk is a multiple of 4 floats, g is 16-byte aligned).  Fixed order: lane
+// stride inside the chunk, a shuffle tree inside the wave, the four waves in index order.  No atomics.
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, long n, long chunk, double* __restrict__ partial) {
+    const long lo = (long)blockIdx.x * chunk;
+    const long hi = (lo + chunk < n) ? lo + chunk : n;
+    const long nvec = (hi - lo) >> 2;
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + lo);
+    double acc = 0.0;
+    long v = threadIdx.x;
+    for (; v + 768 < nvec; v += 1024) {
+        const float4 a = g4[v], b = g4[v + 256], c = g4[v + 512], d = g4[v + 768];
+        acc = sumsq4(sumsq4(sumsq4(sumsq4(acc, a), b), c), d);
+    }
+    for (; v < nvec; v += 256) acc = sumsq4(acc, g4[v]);
+    const long t = lo + (nvec << 2) + threadIdx.x;
+    if (t < hi) acc += (double)g[t] * (double)g[t];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    __shared__ double s[4];
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((s[0] + s[1]) + s[2]) + s[3];
+}
+
+// Stage 2 (one workgroup): the partials summed in a fixed order -- 256 contiguous runs in index order, then the runs in index
+// order -- and the control record (svae_guard_control) of the step written by one lane: norm, clip coefficient with the
+// arithmetic of torch.nn.utils.clip_grad_norm_, go/no-go, and Adam's two bias corrections from the DEVICE-resident step
+// count (formed in double like svae_adam_step forms them on the host, then rounded), plus the running statistics.
+__global__ void __launch_bounds__(256) grad_guard_control_kernel(const double* __restrict__ partial, int nparts, float max_norm,
+                                                                 float lr, float b1, float b2, svae_guard_control* __restrict__ ctl) {
+    __shared__ double s[256];
+    const int per = (nparts + 255) / 256;
+    const int lo = threadIdx.x * per;
+    const int hi = (lo + per < nparts) ? lo + per : nparts;
+    double acc = 0.0;
+    for (int i = lo; i < hi; ++i) acc += partial[i];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double sum = 0.0;
+    for (int k = 0; k < 256; ++k) sum += s[k];
+    const float total = (float)sqrt(sum);
+    const bool finite = isfinite(total);       // a NaN or inf anywhere, or a norm beyond the float range, gives false
+    const float coef = fminf(1.0f, max_norm / (total + 1e-6f));
+    ctl->total = total;
+    ctl->coef = coef;
+    ctl->finite = finite ? 1 : 0;
+    ctl->apply = finite ? 1 : 0;
+    ctl->steps += 1;
+    if (finite) {
+        const long long t = ctl->t + 1;
+        ctl->t = t;
+        ctl->step_size = (float)((double)lr / (1.0 - pow((double)b1, (double)t)));
+        ctl->sqrt_bc2 = (float)sqrt(1.0 - pow((double)b2, (double)t));
+        if (coef < 1.0f) ctl->clipped += 1;
+        ctl->norm_sum += (double)total;
+        ctl->norm_max = fmaxf(ctl->norm_max, total);
+    } else {
+        ctl->skipped += 1;
+    }
+}
+
+// adam_kernel's arithmetic with the step's scale, bias corrections and go/no-go read from the control record: g * coef is
+// formed on load (no scaling pass over the buffer), and a no-go step writes nothing to p, m or v.  The gradient is cleared
+// behind it when zero_grad is set, go or no-go.
+__global__ void adam_guarded_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                    long n, float b1, float b2, float eps, int zero_grad,
+                                    const svae_guard_control* __restrict__ ctl) {
+    const int apply = ctl->apply;
+    const float coef = ctl->coef, step_size = ctl->step_size, sqrt_bc2 = ctl->sqrt_bc2;
+    const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (!apply && !zero_grad) return;
+    if (i + 3 < n) {
+        if (apply) {
+            const float4 g4 = *reinterpret_cast<const float4*>(g + i);
+            float4 m4 = *reinterpret_cast<float4*>(m + i), v4 = *reinterpret_cast<float4*>(v + i), p4 = *reinterpret_cast<float4*>(p + i);
+            const float gg[4] = {g4.x * coef, g4.y * coef, g4.z * coef, g4.w * coef};
+            float mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w}, pp[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                mm[e] = b1 * mm[e] + (1.0f - b1) * gg[e];
+                vv[e] = b2 * vv[e] + (1.0f - b2) * gg[e] * gg[e];
+                pp[e] += -step_size * (mm[e] / (sqrtf(vv[e]) / sqrt_bc2 + eps));
+            }
+            *reinterpret_cast<float4*>(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+            *reinterpret_cast<float4*>(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+            *reinterpret_cast<float4*>(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+        }
+        if (zero_grad) *reinterpret_cast<float4*>(g + i) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    } else {
+        for (long j = i; j < n; ++j) {
+            if (apply) {
+                const float gj = g[j] * coef;
+                const float mj = b1 * m[j] + (1.0f - b1) * gj, vj = b2 * v[j] + (1.0f - b2) * gj * gj;
+                m[j] = mj;
+                v[j] = vj;
+                p[j] += -step_size * (mj / (sqrtf(vj) / sqrt_bc2 + eps));
+            }
+            if (zero_grad) g[j] = 0.0f;
+        }
+    }
+}
+
 }  // namespace svae

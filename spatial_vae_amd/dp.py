@@ -312,9 +312,18 @@ class TrainStep(object):
     scaling pass over the gradient buffer).  A rank whose slice is EMPTY (ragged last batch smaller than the world)
     skips forward and backward but still joins both collectives with zeros.  After the call `metrics` holds
     (elbo, log_p, kl) of the GLOBAL minibatch on every rank, valid until the next call.
+
+    Gradient guard (off by default; the reference has none): clip_grad_norm=X clips the global L2 norm of the gradient at X
+    (torch.nn.utils.clip_grad_norm_'s arithmetic), skip_nonfinite=True leaves parameters, moments and the step count alone
+    when that norm is not finite (the gradient is still cleared).  It runs AFTER the collectives, over grads.flat (every
+    gradient, the layers LowRankExchange.finish() writes included; the metric tail excluded): each rank computes it on
+    identical bits in the same fixed order, so the replicas stay bit-equal without a further collective.  On a GPU it is two
+    small kernels and a variant of the Adam kernel (ops.FlatAdam) and the step still reads nothing back; with torch.optim.Adam
+    (CPU) the same semantics in torch ops.  guard_stats() reports what it did.
     """
 
-    def __init__(self, p_net, q_net, eval_minibatch, lr=1e-4, fused_adam=None, bucketed=None, **eval_kwargs):
+    def __init__(self, p_net, q_net, eval_minibatch, lr=1e-4, fused_adam=None, bucketed=None, clip_grad_norm=None,
+                 skip_nonfinite=False, **eval_kwargs):
         self.p_net, self.q_net = p_net, q_net
         self.eval_minibatch = eval_minibatch
         self.eval_kwargs = eval_kwargs
@@ -377,9 +386,18 @@ class TrainStep(object):
         self._seeds = {}
         self.master = torch.nn.Parameter(self.grads.flat_param)
         self.master.grad = self.grads.flat
+        self.guarded = clip_grad_norm is not None or bool(skip_nonfinite)
+        self.clip_grad_norm = float("inf") if clip_grad_norm is None else float(clip_grad_norm)
+        if not self.clip_grad_norm > 0:
+            raise ValueError("TrainStep: clip_grad_norm must be > 0, got %r" % (clip_grad_norm,))
+        if self.guarded and fused_adam and on_gpu:
+            raise RuntimeError("TrainStep: clip_grad_norm / skip_nonfinite cannot be combined with fused_adam=True: the guarded "
+                               "step is not captured into a HIP graph")
+        self._host_stats = self._fresh_stats()     # the guard's statistics where torch.optim.Adam steps (see _guarded_torch_step)
         if on_gpu and fused_adam is None:
             from .ops import FlatAdam    # torch.optim.Adam's arithmetic in one small kernel over the flat buffer
-            self.optim = FlatAdam([self.master], lr=lr, zero_grad=True)   # the update clears the flat gradient behind itself
+            # the update clears the flat gradient behind itself
+            self.optim = FlatAdam([self.master], lr=lr, zero_grad=True, max_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
         else:
             kw = {"fused": True, "capturable": True} if (fused_adam and on_gpu) else {}
             self.optim = torch.optim.Adam([self.master], lr=lr, **kw)
@@ -423,7 +441,7 @@ class TrainStep(object):
         if torch.is_tensor(st["step"]):
             st["step"].fill_(count)             # torch.optim.Adam keeps a tensor
         else:
-            st["step"] = int(count)             # ops.FlatAdam a Python int
+            st["step"] = int(count)             # ops.FlatAdam a Python int (a device tensor under the gradient guard)
 
     def _adam_state(self):
         """The optimiser's state for the flat master, created (zero moments, step 0) the way the optimiser's first step would
@@ -435,7 +453,7 @@ class TrainStep(object):
                 on_device = bool(group.get("capturable") or group.get("fused"))
                 st["step"] = torch.zeros((), dtype=torch.float32, device=self.master.device if on_device else "cpu")
             else:
-                st["step"] = 0
+                return self.optim.init_state(self.master)       # ops.FlatAdam: guarded, the count lives on the device
             st["exp_avg"] = torch.zeros_like(self.master, memory_format=torch.preserve_format)
             st["exp_avg_sq"] = torch.zeros_like(self.master, memory_format=torch.preserve_format)
         return st
@@ -598,8 +616,52 @@ class TrainStep(object):
             self.grads.tail.zero_()
             self.metrics = self.grads.tail
         self._reduce(global_batch)
-        self.optim.step()
+        if self.guarded and not hasattr(self.optim, "guard_stats"):
+            self._guarded_torch_step()
+        else:
+            self.optim.step()                             # ops.FlatAdam runs the guard itself, on the device
         self.grads.zero(already_cleared=getattr(self.optim, "zero_grad_in_step", False))
+        return out
+
+    # ---- gradient guard where torch.optim.Adam steps (CPU) ------------------------------------------
+    @staticmethod
+    def _fresh_stats():
+        return {"steps": 0, "clipped": 0, "skipped": 0, "norm_sum": 0.0, "max_norm": 0.0, "last_norm": 0.0}
+
+    def _guarded_torch_step(self):
+        """clip_grad_norm_ and the finite check with torch ops on grads.flat, then optim.step() -- or, on a non-finite norm,
+        no step at all (torch.optim.Adam then leaves parameters, moments and its count alone) and a cleared gradient.  The
+        bool() below reads the norm: free on the CPU, where this path runs."""
+        flat = self.grads.flat
+        total = torch.linalg.vector_norm(flat)
+        hs = self._host_stats
+        hs["steps"] += 1
+        hs["last_norm"] = float(total)
+        if not bool(torch.isfinite(total)):
+            hs["skipped"] += 1
+            flat.zero_()
+            return
+        coef = torch.clamp(self.clip_grad_norm / (total + 1e-6), max=1.0)
+        hs["clipped"] += int(float(coef) < 1.0)
+        hs["norm_sum"] += float(total)
+        hs["max_norm"] = max(hs["max_norm"], float(total))
+        flat.mul_(coef)
+        self.optim.step()
+
+    def guard_stats(self, reset=False):
+        """{steps, clipped, skipped, mean_norm, max_norm, last_norm} of the guard since the last reset.  With ops.FlatAdam this
+        is the one call that reads the control record back (it synchronises); the step never does."""
+        if not self.guarded:
+            raise RuntimeError("TrainStep.guard_stats: built without clip_grad_norm / skip_nonfinite")
+        if hasattr(self.optim, "guard_stats"):
+            return self.optim.guard_stats(reset=reset)
+        hs = self._host_stats
+        applied = hs["steps"] - hs["skipped"]
+        out = {"steps": hs["steps"], "clipped": hs["clipped"], "skipped": hs["skipped"],
+               "mean_norm": hs["norm_sum"] / applied if applied else float("nan"), "max_norm": hs["max_norm"],
+               "last_norm": hs["last_norm"]}
+        if reset:
+            self._host_stats = dict(self._fresh_stats(), last_norm=hs["last_norm"])
         return out
 
     def __call__(self, x, *batch, weight=1.0, **kw):
@@ -616,6 +678,8 @@ class TrainStep(object):
         graph from torch's graph-safe Philox generator, as the reference draws it on the device."""
         if world_size() > 1:
             raise RuntimeError("graph capture is wired for the single-GPU step only")
+        if self.guarded:
+            raise RuntimeError("graph capture of the guarded step (clip_grad_norm / skip_nonfinite) is not supported")
         self._static_x = x
         self._static_batch = [b.clone() if torch.is_tensor(b) else b for b in batch]
         self._static_kw = dict(kw)

@@ -523,13 +523,59 @@ def ctf_filter(table, n, m, scale=1.0, device=None):
 
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam's update (amsgrad off, no weight decay) for ONE flat fp32 CUDA parameter, executed by
-    svae_adam_step.  Same defaults and state names (step, exp_avg, exp_avg_sq) as torch.optim.Adam."""
+    svae_adam_step.  Same defaults and state names (step, exp_avg, exp_avg_sq) as torch.optim.Adam.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, zero_grad=False):
+    max_grad_norm / skip_nonfinite switch step() to the guarded pair of calls (svae_grad_guard_norm +
+    svae_adam_step_guarded): torch.nn.utils.clip_grad_norm_(p, max_grad_norm) and "leave parameters and moments alone when
+    the gradient's norm is not finite", decided on the device -- step() reads nothing back.  skip_nonfinite alone clips at
+    +inf, i.e. never.  In that mode state["step"] is a one-element int64 CUDA tensor (torch.optim.Adam's own convention for
+    a device-resident count) aliasing the control record's `t`: it counts the updates APPLIED."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, zero_grad=False, max_grad_norm=None,
+                 skip_nonfinite=False):
         """zero_grad=True: step() also clears each parameter's .grad buffer in the same kernel (the loop's
         optim.zero_grad(), train_mnist.py:150, without a second pass)."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self.zero_grad_in_step = bool(zero_grad)
+        self.guarded = max_grad_norm is not None or bool(skip_nonfinite)
+        self.max_grad_norm = math.inf if max_grad_norm is None else float(max_grad_norm)
+        if not self.max_grad_norm > 0:
+            raise ValueError("FlatAdam: max_grad_norm must be > 0, got %r" % (max_grad_norm,))
+        if self.guarded and sum(len(g["params"]) for g in self.param_groups) != 1:
+            raise RuntimeError("FlatAdam: the gradient guard takes the GLOBAL norm of one flat parameter; got several")
+
+    def init_state(self, p):
+        """The state the first step() would create (zero moments, step 0); guarded: plus the zeroed control record."""
+        st = self.state[p]
+        if not st:
+            if self.guarded:
+                _require_hip(p, "FlatAdam parameter")
+                words = (ctypes.sizeof(_lib.GuardControl) + 7) // 8
+                st["guard"] = torch.zeros(words, dtype=torch.int64, device=p.device)     # all zero bytes = a fresh record
+                st["step"] = st["guard"][:1]                                             # svae_guard_control.t
+            else:
+                st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p)
+            st["exp_avg_sq"] = torch.zeros_like(p)
+        return st
+
+    def guard_stats(self, reset=False):
+        """{steps, clipped, skipped, mean_norm, max_norm, last_norm} since the last reset, read from the control record: the
+        ONE place of the guard that synchronises.  reset=True clears the statistics (not the step count) behind the read."""
+        if not self.guarded:
+            raise RuntimeError("FlatAdam.guard_stats: built without max_grad_norm / skip_nonfinite")
+        p = self.param_groups[0]["params"][0]
+        rec = _lib.GuardControl()
+        st = self.state.get(p)
+        if st:
+            raw = st["guard"].cpu().numpy().tobytes()
+            ctypes.memmove(ctypes.byref(rec), raw, ctypes.sizeof(rec))
+            if reset:
+                st["guard"][_lib.GuardControl.steps.offset // 8:].zero_()
+        applied = rec.steps - rec.skipped
+        return {"steps": int(rec.steps), "clipped": int(rec.clipped), "skipped": int(rec.skipped),
+                "mean_norm": rec.norm_sum / applied if applied else float("nan"), "max_norm": float(rec.norm_max),
+                "last_norm": float(rec.total)}
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -542,13 +588,20 @@ class FlatAdam(torch.optim.Optimizer):
                 _require_hip(p, "FlatAdam parameter")
                 if p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
                     raise RuntimeError("FlatAdam needs contiguous fp32 parameters and gradients")
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p)
-                    st["exp_avg_sq"] = torch.zeros_like(p)
+                st = self.init_state(p)
+                zero = 1 if self.zero_grad_in_step else 0
+                if self.guarded:
+                    ws_bytes = L.svae_grad_guard_workspace_bytes(p.numel())
+                    ws = _buf(p.device, ws_bytes, "guard")
+                    with torch.cuda.device(p.device):
+                        _lib.check(L.svae_grad_guard_norm(p.grad.data_ptr(), p.numel(), self.max_grad_norm, group["lr"], b1, b2,
+                                                          st["guard"].data_ptr(), ws.data_ptr(), ws.numel(), _stream(p.device)))
+                        _lib.check(L.svae_adam_step_guarded(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
+                                                            st["exp_avg_sq"].data_ptr(), p.numel(), b1, b2, group["eps"], zero,
+                                                            st["guard"].data_ptr(), _stream(p.device)))
+                    continue
                 st["step"] += 1
                 with torch.cuda.device(p.device):
                     _lib.check(L.svae_adam_step(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
                                                 st["exp_avg_sq"].data_ptr(), p.numel(), group["lr"], b1, b2, group["eps"],
-                                                st["step"], 1 if self.zero_grad_in_step else 0, _stream(p.device)))
+                                                st["step"], zero, _stream(p.device)))

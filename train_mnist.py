@@ -48,6 +48,12 @@ def mnist_arguments(argv=None):
     p.add_argument("--checkpoint_interval", type=int, default=0, metavar="N",
                    help="write <prefix>_state_epoch<NN>.ckpt (parameters, Adam moments, step count, generator states, table rows) "
                         "beside the .sav files after every N-th epoch and after the last one (0 = never)")
+    p.add_argument("--clip_grad_norm", type=float, default=None, metavar="X",
+                   help="clip the global L2 norm of the gradient at X before every Adam update (the arithmetic of "
+                        "torch.nn.utils.clip_grad_norm_, on the device; default: off -- the reference does not clip)")
+    p.add_argument("--skip_nonfinite", action="store_true",
+                   help="skip the Adam update of a step whose gradient norm is NaN or inf: parameters, moments and the step count "
+                        "stay as they are (default: off -- the reference applies it)")
     return p.parse_args(argv)
 
 
