@@ -853,8 +853,10 @@ __global__ void gaussian_kernel(const float* __restrict__ yp, const float* __res
 // ((n + k - 1)^2 floats; 78 x 78 for 40 x 40 particles with a 39 x 39 filter) and the filter (rows zero-padded to a
 // multiple of 4 taps) sit in LDS; a thread produces 4 consecutive outputs of a row, 4 taps at a time, from two 16-byte
 // reads of the image row and one (broadcast) of the filter row per 16 multiply-adds, no bounds tests.  Every output
-// still accumulates its taps in the reference's (u, v) order and the padding only adds exact zeros, so results equal
-// gaussian_kernel's bit for bit.  512 threads: the 400 (row, column group) tasks of a 40 x 40 image run in one round.
+// still accumulates its taps in the reference's (u, v) order and the padding only adds exact zeros, so the filtered image
+// and dll equal gaussian_kernel's bit for bit.  loglik does not above 256 pixels: the per-pixel terms are the same, but 512
+// threads group their sum differently than 256 do, so the two forms agree to rounding there (equal bits up to 256 pixels,
+// where a thread holds one term at most).  512 threads: the 400 (row, column group) tasks of a 40 x 40 image run in one round.
 constexpr int kCtfThreads = 512;
 struct CtfLds {
     int W, Wp, kp, M;  // padded side, its row stride, padded filter row, left margin of the adjoint's image
