@@ -219,6 +219,43 @@ int svae_elbo_head_backward(const float* g_elbo, const float* g_logp, const floa
                             svae_stream_t stream);
 
 /*
+ * K-sample importance-weighted bound (IWAE; the reference has one sample and the analytic KL only):
+ *   L_b = log( (1/K) sum_k p(x_b | z_bk) p(z_bk) / q(z_bk | x_b) ),   z_bk = exp(logstd_b) * r_bk + mu_b.
+ * K samples of B images are B*K rows to the decoder and the log-likelihood calls; row b*K + k is sample k of image b
+ * everywhere below.  1 <= K <= SVAE_IW_MAX_SAMPLES and B*K < 2^31, SVAE_E_INVALID otherwise.
+ *
+ * svae_latent_iw_forward: the latent head for K draws per image from ONE encoder output (q_out stays (B, 2*inf_dim), read
+ * per image, never replicated).  Pose split, dx_scale and z_scale as in svae_latent_forward:
+ *   r (B*K, inf_dim); theta (B*K) iff rotate; dx (B*K, 2) iff translate; zc (B*K, inf_dim - rotate - 2*translate) iff non-empty
+ *   log_ratio[bk] = log p(z_bk) - log q(z_bk | x_b), summed over all latent coordinates (the log(2 pi)/2 terms cancel):
+ *     log q = sum_j (-logstd_j - r_j^2 / 2),   log p = sum_j (-log sigma_j - (z_j - m_j)^2 / (2 sigma_j^2)),
+ *     sigma = theta_prior for the rotation coordinate and 1 elsewhere; m = 0, except for the rotation coordinate when
+ *     mu_penalty = 0, where m = mu (z - m = std * r): the prior centred on the posterior mean that train_galaxy.py:98-99 /
+ *     train_particles.py:85-86 imply by dropping the mu^2 term.
+ * By construction E_r[-log_ratio[bk]] = kl[b] of svae_latent_forward for the same descriptor and q_out.
+ * svae_latent_iw_backward: g_* are d(loss)/d(output) (NULL = zero); g_q_out (B, 2*inf_dim) is overwritten with the sum over
+ * each image's K samples, taken in an order that depends on K only (no atomics).
+ *
+ * svae_iw_head_forward: with a = loglik + log_ratio (each (B*K)),
+ *   L_b = max_k a + log sum_k exp(a - max) - log K,   weights (B*K) = softmax_k(a),
+ *   out3 = {mean_b L_b, mean_bk loglik, mean_bk(-log_ratio)}: the bound, log p(x|z) and a Monte-Carlo estimate of the KL.
+ * For K >= 2 out3[0] is NOT out3[1] - out3[2].  Fixed summation order over K and B.  A row of equal a gives weights 1/K; an
+ * a far above the rest leaves the other weights exactly 0; a = -inf for some k gives those samples weight 0.
+ * svae_iw_head_backward: dloglik = g_bound * w / B + g_logp / (B K), dlog_ratio = g_bound * w / B - g_kl / (B K);
+ * g_* are device scalars or null.
+ */
+#define SVAE_IW_MAX_SAMPLES 1024
+int svae_latent_iw_forward(const svae_latent_desc* d, int32_t K, const float* q_out, const float* r, float* theta, float* dx,
+                           float* zc, float* log_ratio, svae_stream_t stream);
+int svae_latent_iw_backward(const svae_latent_desc* d, int32_t K, const float* q_out, const float* r, const float* g_theta,
+                            const float* g_dx, const float* g_zc, const float* g_log_ratio, float* g_q_out,
+                            svae_stream_t stream);
+int svae_iw_head_forward(const float* loglik, const float* log_ratio, int32_t B, int32_t K, float* out3, float* weights,
+                         svae_stream_t stream);
+int svae_iw_head_backward(const float* g_bound, const float* g_logp, const float* g_kl, const float* weights, int32_t B,
+                          int32_t K, float* dloglik, float* dlog_ratio, svae_stream_t stream);
+
+/*
  * out[c] = sum_r x[r][c] for a row-major (rows, cols) fp32 matrix, fixed summation order: the bias gradient of a Linear
  * layer (the encoder's, whose weight gradients torch computes with hipBLASLt).
  */

@@ -14,6 +14,7 @@ ACT = {"tanh": 0, "leakyrelu": 1, "relu": 2, "sigmoid": 3}
 FLAG_RESID, FLAG_BILINEAR, FLAG_SOFTPLUS = 1, 2, 4
 
 ABI_VERSION = 2
+IW_MAX_SAMPLES = 1024       # SVAE_IW_MAX_SAMPLES
 
 
 # every function include/svae.h declares; build() and tests/test_host_cpu.py re-derive this list from the header and check it
@@ -22,8 +23,9 @@ EXPORTS = ("svae_abi_version", "svae_adam_step", "svae_adam_step_guarded", "svae
            "svae_ctf_filter_workspace_bytes", "svae_decoder_backward", "svae_decoder_forward",
            "svae_decoder_forward_bce", "svae_elbo_head_backward", "svae_elbo_head_forward", "svae_gaussian_loglik",
            "svae_gaussian_workspace_bytes", "svae_gemm_mode_get", "svae_gemm_mode_set", "svae_grad_guard_control_bytes",
-           "svae_grad_guard_norm", "svae_grad_guard_workspace_bytes", "svae_last_error",
-           "svae_latent_backward", "svae_latent_forward", "svae_linear_backward", "svae_linear_forward",
+           "svae_grad_guard_norm", "svae_grad_guard_workspace_bytes", "svae_iw_head_backward", "svae_iw_head_forward",
+           "svae_last_error", "svae_latent_backward", "svae_latent_forward", "svae_latent_iw_backward",
+           "svae_latent_iw_forward", "svae_linear_backward", "svae_linear_forward",
            "svae_path_counts", "svae_path_name", "svae_profile_enable", "svae_profile_kind_name",
            "svae_profile_read", "svae_rotate_bicubic", "svae_saved_bytes", "svae_workspace_bytes")
 
@@ -116,6 +118,14 @@ def lib():
     L.svae_elbo_head_forward.argtypes = [vp, vp, i32, vp, vp]
     L.svae_elbo_head_backward.restype = ctypes.c_int
     L.svae_elbo_head_backward.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    L.svae_latent_iw_forward.restype = ctypes.c_int
+    L.svae_latent_iw_forward.argtypes = [ctypes.POINTER(LatentDesc), i32, vp, vp, vp, vp, vp, vp, vp]
+    L.svae_latent_iw_backward.restype = ctypes.c_int
+    L.svae_latent_iw_backward.argtypes = [ctypes.POINTER(LatentDesc), i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.svae_iw_head_forward.restype = ctypes.c_int
+    L.svae_iw_head_forward.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.svae_iw_head_backward.restype = ctypes.c_int
+    L.svae_iw_head_backward.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.svae_colsum.restype = ctypes.c_int
     L.svae_colsum.argtypes = [vp, i32, i32, vp, vp]
     L.svae_linear_forward.restype = ctypes.c_int

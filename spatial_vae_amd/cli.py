@@ -11,7 +11,8 @@ interactive "clear outputs?" prompt (the run directory is created, never wiped),
 archive and dataset download.  `--augment_rotation` runs on the device
 (ops.rotate_augment, bit-identical to the reference's per-image Pillow loop).  Added: `--synthetic N`
 (train on N synthetic images when no data files exist), data-parallel execution under torchrun, and
-`--progress_every` (the reference pays three .item() syncs per step for its progress line).
+`--progress_every` (the reference pays three .item() syncs per step for its progress line), and `--num_samples K` /
+`--eval_num_samples K` (the K-sample importance-weighted bound for the training / validation passes; 1 = the reference).
 """
 import copy
 import math
@@ -81,16 +82,18 @@ def loader_order(n, shuffle):
     return torch.randperm(n, generator=g)
 
 
-def pass_noise(sizes, inf_dim, device, after_first=()):
+def pass_noise(sizes, inf_dim, device, after_first=(), num_samples=1):
     """The N(0,1) draws of one pass over minibatches of `sizes` images, from torch's global CPU generator in the reference's
     order and shapes: one x.data.new(B, inf_dim).normal_() per minibatch (train_mnist.py:38; CPU tensors in the CPU reference),
     and -- on a pass that dumps images -- the display helpers' draws right after the first minibatch's (`after_first`: their
     shapes; train_mnist.py:107, train_galaxy.py:146, :177).  The shapes matter: the CPU normal_ kernel fills in blocks of 16 and
     re-draws the tail, so one big draw is not the concatenation of the small ones.  Returns (per-minibatch device tensors,
-    display draws on the device); everything is uploaded in ONE transfer, nothing is drawn or copied inside the step loop."""
+    display draws on the device); everything is uploaded in ONE transfer, nothing is drawn or copied inside the step loop.
+    num_samples=K: ONE (b*K, inf_dim) draw per minibatch (row i*K + k = sample k of image i), so K = 1 consumes the generator
+    exactly as before; the display helpers stay single-sample."""
     draws, extra = [], []
     for i, b in enumerate(sizes):
-        draws.append(torch.empty(b, inf_dim).normal_())
+        draws.append(torch.empty(b * num_samples, inf_dim).normal_())
         if i == 0:
             extra = [torch.empty(*shape).normal_() for shape in after_first]
     flat = torch.cat([t.reshape(-1) for t in draws + extra]) if draws else torch.empty(0)
@@ -102,23 +105,23 @@ def pass_noise(sizes, inf_dim, device, after_first=()):
     return out[:len(draws)], out[len(draws):]
 
 
-def train_pass_plan(N, bs, inf_dim, device, home=None):
+def train_pass_plan(N, bs, inf_dim, device, home=None, num_samples=1):
     """(index minibatches, their noise) of one training pass: iter(DataLoader(shuffle=True)) then one draw per minibatch
     (train_mnist.py:138-143 via :38).  The last minibatch is ragged, as the reference's loader keeps it (no drop_last)."""
     perm = loader_order(N, True)
     batches = [perm[i:i + bs].to(home if home is not None else device) for i in range(0, N, bs)]
-    noise, _ = pass_noise([b.numel() for b in batches], inf_dim, device)
+    noise, _ = pass_noise([b.numel() for b in batches], inf_dim, device, num_samples=num_samples)
     return batches, noise
 
 
-def eval_pass_plan(ntest, bs, inf_dim, device, home=None, display_shapes=()):
+def eval_pass_plan(ntest, bs, inf_dim, device, home=None, display_shapes=(), num_samples=1):
     """(index minibatches, their noise, the display helpers' noise) of one evaluation pass over the un-shuffled validation
     loader (train_mnist.py:196-201); on a dump epoch eval_model decodes the first minibatch again for the PNG files
     (train_mnist.py:214-224, train_galaxy.py:275-292) -- `display_shapes` maps a minibatch size to those draws' shapes."""
     order = loader_order(ntest, False)
     tb = [order[i:i + bs].to(home if home is not None else device) for i in range(0, ntest, bs)]
     shapes = display_shapes(tb[0].numel()) if (display_shapes and tb) else ()
-    noise, shown = pass_noise([b.numel() for b in tb], inf_dim, device, after_first=shapes)
+    noise, shown = pass_noise([b.numel() for b in tb], inf_dim, device, after_first=shapes, num_samples=num_samples)
     return tb, noise, shown
 
 
@@ -216,7 +219,7 @@ CHECKPOINT_VERSION = 1
 RESUME_FREE_ARGS = {"num_epochs", "save_prefix", "device", "progress_every", "resume", "checkpoint_interval", "no_preload",
                     "train_path", "test_path", "logging_level"}
 # Arguments added after state files were first written, with the value that reproduces the run of a file that lacks them.
-RESUME_ARG_DEFAULTS = {"clip_grad_norm": None, "skip_nonfinite": False}
+RESUME_ARG_DEFAULTS = {"clip_grad_norm": None, "skip_nonfinite": False, "num_samples": 1, "eval_num_samples": 1}
 
 
 class CheckpointError(SystemExit):
@@ -299,7 +302,8 @@ def check_resume_args(ck, args, script):
     free = set(RESUME_FREE_ARGS)
     if script == "particles":
         free.add("save_interval")           # particles dumps no images: the interval only decides when .sav files are written
-    stored = dict(RESUME_ARG_DEFAULTS, **ck["args"])     # a file written before the gradient guard existed: both options off
+    # a file written before the gradient guard / the sample counts existed: both guard options off, one sample per image
+    stored = dict(RESUME_ARG_DEFAULTS, **ck["args"])
     now = dict(RESUME_ARG_DEFAULTS, **now)
     for k in sorted(set(stored) | set(now)):
         if k in free:
@@ -353,8 +357,12 @@ def run_epoch(script, step, x, batches, train, N, epoch, num_epochs, rank, world
     so are the augmentation angles, so a G-rank step computes what the 1-rank step computes (up to fp32 summation
     order).  Training metrics come back inside the gradient all-reduce (step.metrics); evaluation metrics are
     collected per batch and all-reduced ONCE per epoch.  A rank with an empty slice (ragged last batch smaller than the
-    world) contributes zeros."""
+    world) contributes zeros.
+
+    extra["num_samples"] = K >= 2: the pass evaluates the K-sample importance-weighted bound.  Shards stay by image; the
+    noise of a global minibatch is (gb*K, inf_dim) and rank g takes rows [lo*K, hi*K)."""
     p_net, q_net = step.p_net, step.q_net
+    K = int(extra.get("num_samples", 1))
     p_net.train(train)
     q_net.train(train)
     data = extra["data"]
@@ -375,8 +383,10 @@ def run_epoch(script, step, x, batches, train, N, epoch, num_epochs, rank, world
         if noise_list is not None:
             r = noise_list[it]
         else:       # no prepared draws: the reference's per-minibatch draw from the global CPU generator (train_mnist.py:38)
-            r = torch.empty(gb, inf_dim).normal_().to(x.device, non_blocking=True)
-        kw["noise"] = r[lo:hi]
+            r = torch.empty(gb * K, inf_dim).normal_().to(x.device, non_blocking=True)
+        kw["noise"] = r[lo * K:hi * K]
+        if K > 1:
+            kw["num_samples"] = K
         out = None
         if train:
             kw.update(extra.get("train_kw", {}))        # augmentation applies to training steps only (train_galaxy.py:204)
@@ -399,7 +409,8 @@ def run_epoch(script, step, x, batches, train, N, epoch, num_epochs, rank, world
             else:
                 mean.update(gb, vals)
         if it == 0 and extra.get("dump") and rank == 0 and out is not None:   # first batch of a save-interval epoch (train_mnist.py:214-224)
-            extra["dump"](y, out[3] if len(out) > 3 else None)
+            # the posed reconstruction shown is each image's first sample
+            extra["dump"](y, (out[3] if K == 1 else out[3][::K]) if len(out) > 3 else None)
         if train and rank == 0 and progress_every > 0 and (it + 1) % progress_every == 0:
             e, g, k = mean.values()
             print("# [{}/{}] training {:.1%}, ELBO={:.5f}, Error={:.5f}, KL={:.5f}".format(
@@ -434,6 +445,8 @@ def train_main(script, args, build):
     skip_nonfinite = bool(getattr(args, "skip_nonfinite", False))
     if clip is not None and not clip > 0:
         raise SystemExit("the gradient-norm threshold must be > 0")
+    train_k = int(getattr(args, "num_samples", 1) or 1)
+    eval_k = int(getattr(args, "eval_num_samples", None) or train_k)
     # Randomness is consumed from torch's GLOBAL CPU generator and np.random in the order the reference's main() consumes
     # them: default initialisation of p_net then q_net, one draw for the sample-image pass over the validation
     # loader, then per epoch the two draws of iter(DataLoader(shuffle=True)), one N(0,1) draw per training minibatch, one draw
@@ -524,11 +537,11 @@ def train_main(script, args, build):
         kw = {}
         if script != "mnist":
             kw["z_scale"] = 0 if epoch < z_delay else 1
-        batches, noise = train_pass_plan(N, bs, inf_dim, device, home)    # same order and draws on every rank
+        batches, noise = train_pass_plan(N, bs, inf_dim, device, home, train_k)    # same order and draws on every rank
         train_kw = {"augment_rotation": True} if cfg.get("augment") and script != "mnist" else {}
         t_epoch = time.time()
         e, g, k = run_epoch(script, step, x, batches, True, N, epoch, num_epochs, rank, world, args.progress_every,
-                            dict(data=tr, mask=mask, kw=kw, train_kw=train_kw, inf_dim=inf_dim, noise=noise))
+                            dict(data=tr, mask=mask, kw=kw, train_kw=train_kw, inf_dim=inf_dim, noise=noise, num_samples=train_k))
         if rank == 0:       # run_epoch's values() synchronised: the epoch's training pass is complete
             print("# epoch {}: {} training images in {:.3f} s = {:.0f} images/s".format(
                 epoch + 1, N, time.time() - t_epoch, N / max(time.time() - t_epoch, 1e-9)), file=sys.stderr)
@@ -542,11 +555,11 @@ def train_main(script, args, build):
         if script != "particles" and (epoch + 1) % args.save_interval == 0:
             # the display helpers' draws are made on every rank (one random stream), the files written by rank 0
             shapes = display_draw_shapes(script, inf_dim, args.z_dim)
-        tb, noise, shown = eval_pass_plan(ntest, bs, inf_dim, device, home, shapes)
+        tb, noise, shown = eval_pass_plan(ntest, bs, inf_dim, device, home, shapes, eval_k)
         if shapes and out_dir:
             dump = _image_dumper(script, step, x, cfg, out_dir, str(epoch + 1).zfill(digits), label, kw, args.z_dim, shown)
         ev = run_epoch(script, step, x, tb, False, ntest, epoch, num_epochs, rank, world, 0,
-                       dict(data=te, mask=mask, kw=kw, dump=dump, inf_dim=inf_dim, noise=noise))
+                       dict(data=te, mask=mask, kw=kw, dump=dump, inf_dim=inf_dim, noise=noise, num_samples=eval_k))
         if rank == 0:
             if script == "particles":
                 rows.append("\t".join([str(epoch + 1), "train", str(e), str(g), str(k)]))

@@ -1382,6 +1382,69 @@ int svae_elbo_head_backward(const float* g_elbo, const float* g_logp, const floa
     return launch_status("svae_elbo_head_backward");
 }
 
+// K samples per image: B * K rows must stay an int32 count, like every other batch size of this interface
+static int iw_samples(const char* who, int32_t B, int32_t K) {
+    if (K < 1 || K > SVAE_IW_MAX_SAMPLES) return fail(SVAE_E_INVALID, "%s: K = %d outside [1, %d]", who, K, SVAE_IW_MAX_SAMPLES);
+    if (B < 1 || (long)B * K > 0x7fffffffL) return fail(SVAE_E_INVALID, "%s: B = %d with K = %d is out of range", who, B, K);
+    return SVAE_OK;
+}
+
+int svae_latent_iw_forward(const svae_latent_desc* d, int32_t K, const float* q_out, const float* r, float* theta, float* dx,
+                           float* zc, float* log_ratio, svae_stream_t stream) {
+    LatentGeo g;
+    int rc;
+    if ((rc = latent_geo(d, &g))) return rc;
+    if ((rc = iw_samples("svae_latent_iw_forward", g.B, K))) return rc;
+    const int zd = g.inf - g.rotate - 2 * g.translate;
+    if (!q_out || !r || !log_ratio || (g.rotate && !theta) || (g.translate && !dx) || (zd > 0 && !zc))
+        return fail(SVAE_E_INVALID, "svae_latent_iw_forward: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_LATENT, st);
+    hipLaunchKernelGGL(latent_iw_fwd_kernel, dim3(blocks_for((long)g.B * K)), dim3(256), 0, st, q_out, r, theta, dx, zc,
+                       log_ratio, K, g);
+    return launch_status("svae_latent_iw_forward");
+}
+
+int svae_latent_iw_backward(const svae_latent_desc* d, int32_t K, const float* q_out, const float* r, const float* g_theta,
+                            const float* g_dx, const float* g_zc, const float* g_log_ratio, float* g_q_out,
+                            svae_stream_t stream) {
+    LatentGeo g;
+    int rc;
+    if ((rc = latent_geo(d, &g))) return rc;
+    if ((rc = iw_samples("svae_latent_iw_backward", g.B, K))) return rc;
+    if (!q_out || !r || !g_q_out) return fail(SVAE_E_INVALID, "svae_latent_iw_backward: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_LATENT, st);
+    int width = 1;                                                   // iw_group_width(K): lanes per (image, latent)
+    while (width < K && width < 64) width <<= 1;
+    hipLaunchKernelGGL(latent_iw_bwd_kernel, dim3(blocks_for((long)g.B * g.inf * width)), dim3(256), 0, st, q_out, r, g_theta,
+                       g_dx, g_zc, g_log_ratio, g_q_out, K, g);
+    return launch_status("svae_latent_iw_backward");
+}
+
+int svae_iw_head_forward(const float* loglik, const float* log_ratio, int32_t B, int32_t K, float* out3, float* weights,
+                         svae_stream_t stream) {
+    int rc;
+    if ((rc = iw_samples("svae_iw_head_forward", B, K))) return rc;
+    if (!loglik || !log_ratio || !out3 || !weights) return fail(SVAE_E_INVALID, "svae_iw_head_forward: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_LATENT, st);
+    hipLaunchKernelGGL(iw_head_fwd_kernel, dim3(1), dim3(256), 0, st, loglik, log_ratio, B, K, out3, weights);
+    return launch_status("svae_iw_head_forward");
+}
+
+int svae_iw_head_backward(const float* g_bound, const float* g_logp, const float* g_kl, const float* weights, int32_t B,
+                          int32_t K, float* dloglik, float* dlog_ratio, svae_stream_t stream) {
+    int rc;
+    if ((rc = iw_samples("svae_iw_head_backward", B, K))) return rc;
+    if (!weights || !dloglik || !dlog_ratio) return fail(SVAE_E_INVALID, "svae_iw_head_backward: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_LATENT, st);
+    hipLaunchKernelGGL(iw_head_bwd_kernel, dim3(blocks_for((long)B * K)), dim3(256), 0, st, g_bound, g_logp, g_kl, weights, B,
+                       K, dloglik, dlog_ratio);
+    return launch_status("svae_iw_head_backward");
+}
+
 int svae_colsum(const float* x, int32_t rows, int32_t cols, float* out, svae_stream_t stream) {
     if (!x || !out || rows < 1 || cols < 1) return fail(SVAE_E_INVALID, "svae_colsum: bad arguments");
     hipStream_t st = static_cast<hipStream_t>(stream);

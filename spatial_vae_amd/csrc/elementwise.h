@@ -1048,6 +1048,165 @@ __global__ void latent_bwd_kernel(const float* __restrict__ q, const float* __re
     gq[(long)b * 2 * g.inf + g.inf + j] = dz * r[idx] * sd + dls;
 }
 
+// ---------------------------------------------------------------- K-sample importance-weighted bound (no counterpart in the reference)
+// Row b*K + k is sample k of image b.  A few thousand elements per call: the arithmetic is done in doubles and rounded once on
+// the way out, so log_ratio (a difference of two sums of like size) and the log-sum-exp carry no error of their own.
+
+// smallest power of two >= K, at most 64: the lanes that share one image (iw_head) or one encoder output (latent_iw_bwd)
+__device__ __forceinline__ int iw_group_width(int K) {
+    int g = 1;
+    while (g < K && g < 64) g <<= 1;
+    return g;
+}
+// sum / max over the G lanes of a group (G a power of two <= 64, groups aligned to G): xor steps below G stay inside it
+__device__ __forceinline__ double iw_group_sum(double v, int G) {
+    for (int s = 1; s < G; s <<= 1) v += __shfl_xor(v, s);
+    return v;
+}
+__device__ __forceinline__ double iw_group_max(double v, int G) {
+    for (int s = 1; s < G; s <<= 1) v = fmax(v, __shfl_xor(v, s));
+    return v;
+}
+
+// one thread per (image, sample): z = exp(logstd_b) * r_bk + mu_b; theta / dx / content; log p(z) - log q(z | x)
+__global__ void latent_iw_fwd_kernel(const float* __restrict__ q, const float* __restrict__ r, float* __restrict__ theta,
+                                     float* __restrict__ dx, float* __restrict__ zc, float* __restrict__ log_ratio, int K,
+                                     LatentGeo g) {
+    const long row = (long)blockIdx.x * 256 + threadIdx.x;
+    if (row >= (long)g.B * K) return;
+    const long b = row / K;
+    const float* mu = q + b * 2 * g.inf;
+    const float* ls = mu + g.inf;
+    const int off = g.rotate ? 1 : 0, c0 = off + (g.translate ? 2 : 0), zd = g.inf - c0;
+    double lp = 0.0, lq = 0.0;
+    for (int j = 0; j < g.inf; ++j) {
+        const double sd = exp((double)ls[j]), rr = r[row * g.inf + j];
+        const double z = sd * rr + (double)mu[j];
+        lq += -(double)ls[j] - 0.5 * rr * rr;
+        if (j < off) {
+            theta[row] = (float)z;
+            const double s = g.theta_prior, d = g.mu_penalty ? z : sd * rr;   // without the mu^2 term the prior sits on mu
+            lp += -log(s) - d * d / (2.0 * s * s);
+        } else {
+            lp += -0.5 * z * z;
+            if (j < c0) dx[2 * row + (j - off)] = (float)(z * (double)g.dx_scale);
+            else zc[row * zd + (j - c0)] = (float)(z * (double)g.z_scale);
+        }
+    }
+    log_ratio[row] = (float)(lp - lq);
+}
+
+// one group of lanes per (image, latent): the K samples' contributions to d/d(mu), d/d(logstd), summed in a fixed order
+__global__ void latent_iw_bwd_kernel(const float* __restrict__ q, const float* __restrict__ r,
+                                     const float* __restrict__ g_theta, const float* __restrict__ g_dx,
+                                     const float* __restrict__ g_zc, const float* __restrict__ g_lr, float* __restrict__ gq,
+                                     int K, LatentGeo g) {
+    const int G = iw_group_width(K);
+    const long item = ((long)blockIdx.x * 256 + threadIdx.x) / G;     // whole groups fall inside or outside: G divides 256
+    const int lane = threadIdx.x & (G - 1);
+    const bool live = item < (long)g.B * g.inf;
+    double dmu = 0.0, dls = 0.0;
+    int j = 0;
+    long b = 0;
+    if (live) {
+        j = (int)(item % g.inf);
+        b = item / g.inf;
+        const float* mu = q + b * 2 * g.inf;
+        const int off = g.rotate ? 1 : 0, c0 = off + (g.translate ? 2 : 0), zd = g.inf - c0;
+        const double sd = exp((double)mu[g.inf + j]), m = mu[j];
+        const double s2 = (double)g.theta_prior * (double)g.theta_prior;
+        for (int k = lane; k < K; k += G) {
+            const long row = b * K + k;
+            const double rr = r[row * g.inf + j], sr = sd * rr, z = sr + m;
+            const double glr = g_lr ? (double)g_lr[row] : 0.0;
+            double dz, pmu, pls;                                     // d(out)/dz seen from above; d(log p)/d(mu), /d(logstd)
+            if (j < off) {
+                dz = g_theta ? (double)g_theta[row] : 0.0;
+                pmu = g.mu_penalty ? -z / s2 : 0.0;
+                pls = g.mu_penalty ? -z * sr / s2 : -sr * sr / s2;
+            } else {
+                if (j < c0) dz = g_dx ? (double)g_dx[2 * row + (j - off)] * (double)g.dx_scale : 0.0;
+                else dz = g_zc ? (double)g_zc[row * zd + (j - c0)] * (double)g.z_scale : 0.0;
+                pmu = -z;
+                pls = -z * sr;
+            }
+            dmu += dz + glr * pmu;
+            dls += dz * sr + glr * (1.0 + pls);                      // - log q contributes + logstd
+        }
+    }
+    dmu = iw_group_sum(dmu, G);
+    dls = iw_group_sum(dls, G);
+    if (live && lane == 0) {
+        gq[b * 2 * g.inf + j] = (float)dmu;
+        gq[b * 2 * g.inf + g.inf + j] = (float)dls;
+    }
+}
+
+// One block.  A group of lanes per image: a = loglik + log_ratio, L_b = max a + log sum exp(a - max) - log K, weights =
+// softmax_k(a); out = {mean_b L_b, mean_bk loglik, mean_bk(-log_ratio)}.  Groups take images g, g + 256/G, ... and the block
+// combines lanes, then waves, in a fixed order.  An image whose a are all -inf gets L_b = -inf and weights 0.
+__global__ void iw_head_fwd_kernel(const float* __restrict__ loglik, const float* __restrict__ log_ratio, int B, int K,
+                                   float* __restrict__ out, float* __restrict__ weights) {
+    __shared__ double red[3][4];
+    const int G = iw_group_width(K), groups = 256 / G;
+    const int grp = threadIdx.x / G, lane = threadIdx.x & (G - 1);
+    double accL = 0.0, accP = 0.0, accR = 0.0;
+    for (int b0 = 0; b0 < B; b0 += groups) {                          // every lane of the block takes every trip: shuffles are safe
+        const int b = b0 + grp;
+        const bool live = b < B;
+        const float* ll = loglik + (long)b * K;
+        const float* lr = log_ratio + (long)b * K;
+        double m = -INFINITY, sp = 0.0, sr = 0.0;
+        if (live)
+            for (int k = lane; k < K; k += G) {
+                m = fmax(m, (double)ll[k] + (double)lr[k]);
+                sp += ll[k];
+                sr += lr[k];
+            }
+        m = iw_group_max(m, G);
+        if (!(m > -INFINITY)) m = 0.0;
+        double s = 0.0;
+        if (live)
+            for (int k = lane; k < K; k += G) s += exp((double)ll[k] + (double)lr[k] - m);
+        s = iw_group_sum(s, G);
+        sp = iw_group_sum(sp, G);
+        sr = iw_group_sum(sr, G);
+        if (live) {
+            for (int k = lane; k < K; k += G)
+                weights[(long)b * K + k] = s > 0.0 ? (float)(exp((double)ll[k] + (double)lr[k] - m) / s) : 0.0f;
+            if (lane == 0) {
+                accL += m + log(s) - log((double)K);
+                accP += sp;
+                accR += sr;
+            }
+        }
+    }
+    double acc[3] = {accL, accP, accR};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        acc[i] = iw_group_sum(acc[i], 64);
+        if ((threadIdx.x & 63) == 0) red[i][threadIdx.x >> 6] = acc[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double n = (double)B * (double)K;
+        out[0] = (float)((red[0][0] + red[0][1] + red[0][2] + red[0][3]) / (double)B);
+        out[1] = (float)((red[1][0] + red[1][1] + red[1][2] + red[1][3]) / n);
+        out[2] = (float)(-(red[2][0] + red[2][1] + red[2][2] + red[2][3]) / n);
+    }
+}
+// d/d loglik[bk] = g_bound * w / B + g_logp / (B K), d/d log_ratio[bk] = g_bound * w / B - g_kl / (B K)
+__global__ void iw_head_bwd_kernel(const float* __restrict__ g_bound, const float* __restrict__ g_logp,
+                                   const float* __restrict__ g_kl, const float* __restrict__ weights, int B, int K,
+                                   float* __restrict__ dloglik, float* __restrict__ dlog_ratio) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)B * K) return;
+    const double ge = g_bound ? g_bound[0] : 0.0f, gl = g_logp ? g_logp[0] : 0.0f, gk = g_kl ? g_kl[0] : 0.0f;
+    const double n = (double)B * (double)K, w = (double)weights[i] / (double)B;
+    dloglik[i] = (float)(ge * w + gl / n);
+    dlog_ratio[i] = (float)(ge * w - gk / n);
+}
+
 // ---------------------------------------------------------------- rotation augmentation (train_galaxy.py:41-54, train_particles.py:31-43)
 // Pillow's Image.rotate(angle, resample=BICUBIC) for a batch of square-or-not images resident in HBM.  The host supplies,
 // per image, the six inverse-affine coefficients exactly as PIL/Image.py computes them (doubles) or an exact quarter-turn

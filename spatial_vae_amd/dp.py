@@ -35,6 +35,18 @@ def env_world():
     return int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
 
 
+def whole_lines(stream):
+    """Make a text stream hand each finished line to the file in ONE write.  The ranks of a job share one stdout (launch_ranks,
+    torchrun).  With PYTHONUNBUFFERED=1 or `python -u` print() writes every argument, separator and the newline on its own, so
+    two ranks that print at the same moment splice their lines into each other ("rank rank 0 1 ...") and whoever reads the
+    job's output loses both.  Line buffering keeps what -u is for -- a line is out as soon as it ends.  A stream that cannot
+    be reconfigured (a test's StringIO) is left alone."""
+    try:
+        stream.reconfigure(line_buffering=True, write_through=False)
+    except (AttributeError, ValueError, OSError):
+        pass
+
+
 def init_process_group(device_is_gpu):
     """Join the job described by RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT (torchrun sets them)."""
     rank, world, local = env_world()
@@ -45,6 +57,8 @@ def init_process_group(device_is_gpu):
     # a rank that never arrives at a collective (a dead peer, a wedged GPU) must end the job, not hang it: every collective
     # of the group carries this limit (SVAE_DP_TIMEOUT seconds, default 300; launch_ranks has its own wall-clock limit on top)
     limit = datetime.timedelta(seconds=int(os.environ.get("SVAE_DP_TIMEOUT", "300")))
+    if world > 1:
+        whole_lines(sys.stdout)
     if world > 1 and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -312,6 +326,10 @@ class TrainStep(object):
     scaling pass over the gradient buffer).  A rank whose slice is EMPTY (ragged last batch smaller than the world)
     skips forward and backward but still joins both collectives with zeros.  After the call `metrics` holds
     (elbo, log_p, kl) of the GLOBAL minibatch on every rank, valid until the next call.
+
+    num_samples=K (an eval_minibatch_* keyword, here or per call) trains on the K-sample importance-weighted bound.  The bound
+    is a mean over images of per-image terms, so shards stay by image and nothing else changes: a rank passes noise rows
+    [lo*K, hi*K) of the global draw.  The torch-only step (CPU parameters) refuses K > 1.
 
     Gradient guard (off by default; the reference has none): clip_grad_norm=X clips the global L2 norm of the gradient at X
     (torch.nn.utils.clip_grad_norm_'s arithmetic), skip_nonfinite=True leaves parameters, moments and the step count alone
@@ -598,6 +616,9 @@ class TrainStep(object):
         rows = batch[0].size(0) if torch.is_tensor(batch[0]) else 1
         if global_batch is None and weight > 0:
             global_batch = int(round(rows / weight))
+        if int(kw.get("num_samples", self.eval_kwargs.get("num_samples", 1))) > 1 and self.device.type != "cuda":
+            raise RuntimeError("TrainStep: num_samples > 1 (the importance-weighted bound) runs through the HIP kernels only; "
+                               "this step holds its parameters on %s" % (self.device,))
         if rows > 0:
             args = dict(self.eval_kwargs)
             args.update(kw)

@@ -95,8 +95,11 @@ def _augment(script, y, rotate, offset):
 
 
 def _core(script, x, y, p_net, q_net, rotate, translate, dx_scale, theta_prior, z_scale, mask, ctf, noise, use_cuda,
-          augment_rotation=False, offset=None):
+          augment_rotation=False, offset=None, num_samples=1):
     B = y.size(0)
+    K = int(num_samples)
+    if K < 1:
+        raise RuntimeError("num_samples must be >= 1, got %d" % K)
     if use_cuda:
         y = y.cuda()
     y_in = y
@@ -107,12 +110,26 @@ def _core(script, x, y, p_net, q_net, rotate, translate, dx_scale, theta_prior, 
     q_out = _encode(q_net, y_in.view(B, -1))
     inf_dim = q_out.size(1) // 2
     # E_q[log p(x|z)] by one reparameterised sample (train_mnist.py:36-39); the draw itself stays a torch call
-    r = noise if noise is not None else torch.empty(B, inf_dim, device=x.device, dtype=q_out.dtype).normal_()
-    # reparameterise + pose split + KL terms in one kernel (train_mnist.py:33-39, 42-72, 61-63, 83-85)
-    theta, dx, zc, kl_b = ops.latent_head(q_out, r, rotate, translate, script == "mnist", dx_scale, z_scale, theta_prior)
+    r = noise if noise is not None else torch.empty(B * K, inf_dim, device=x.device, dtype=q_out.dtype).normal_()
+    if K > 1:
+        # the K-sample importance-weighted bound: one encoder output per image, K draws from it; from here to the head the
+        # B * K samples are B * K images to the unchanged decoder and likelihood kernels (row b * K + k = sample k of image b)
+        if tuple(r.shape) != (B * K, inf_dim):
+            raise RuntimeError("noise must be (%d, %d) for %d samples of %d images, got %s"
+                               % (B * K, inf_dim, K, B, tuple(r.shape)))
+        theta, dx, zc, kl_b = ops.latent_head_iw(q_out, r, K, rotate, translate, script == "mnist", dx_scale, z_scale,
+                                                 theta_prior)       # kl_b: log p(z) - log q(z|x) per sample
+        y = y.repeat_interleave(K, 0)
+        if ctf is not None:
+            ctf = ctf.repeat_interleave(K, 0)
+        B = B * K
+    else:
+        # reparameterise + pose split + KL terms in one kernel (train_mnist.py:33-39, 42-72, 61-63, 83-85)
+        theta, dx, zc, kl_b = ops.latent_head(q_out, r, rotate, translate, script == "mnist", dx_scale, z_scale, theta_prior)
     if offset is not None and np.any(offset > 0):
         # invert the random rotation: reconstruct the original with the offset added (train_galaxy.py:84-87)
-        theta = theta + torch.from_numpy(offset).float().to(theta.device)
+        turn = torch.from_numpy(offset).float().to(theta.device)
+        theta = theta + (turn.repeat_interleave(K) if K > 1 else turn)
 
     loglik = None
     if hasattr(p_net, "forward_posed"):
@@ -127,32 +144,36 @@ def _core(script, x, y, p_net, q_net, rotate, translate, dx_scale, theta_prior, 
         loglik = ops.gaussian_loglik(y_hat.reshape(B, -1), y.view(B, -1), mask=mask, ctf=ctf)
     elif loglik is None:
         loglik = ops.bce_loglik(y_hat.reshape(B, -1), y.reshape(B, -1))
-    elbo, log_p_x_g_z, kl_div = ops.elbo_head(loglik, kl_b)     # the two batch means and their difference, one kernel
+    if K > 1:
+        elbo, log_p_x_g_z, kl_div = ops.iw_head(loglik, kl_b, K)    # log-mean-exp over each image's samples, then the batch means
+    else:
+        elbo, log_p_x_g_z, kl_div = ops.elbo_head(loglik, kl_b)     # the two batch means and their difference, one kernel
     return elbo, log_p_x_g_z, kl_div, y_hat, logits
 
 
 def eval_minibatch_mnist(x, y, p_net, q_net, rotate=True, translate=True, dx_scale=0.1, theta_prior=math.pi,
-                         use_cuda=False, noise=None, return_logits=False):
+                         use_cuda=False, noise=None, return_logits=False, num_samples=1):
     elbo, log_p, kl, y_hat, logits = _core("mnist", x, y, p_net, q_net, rotate, translate, dx_scale, theta_prior, 1,
-                                           None, None, noise, use_cuda)
-    out = (elbo, log_p, kl, y_hat.view(y.size(0), -1))
+                                           None, None, noise, use_cuda, num_samples=num_samples)
+    out = (elbo, log_p, kl, y_hat.view(y.size(0) * num_samples, -1))
     return out + (logits,) if return_logits else out
 
 
 def eval_minibatch_galaxy(x, y, p_net, q_net, rotate=True, translate=True, dx_scale=0.1, theta_prior=math.pi,
-                          augment_rotation=False, z_scale=1, use_cuda=False, noise=None, return_logits=False, offset=None):
+                          augment_rotation=False, z_scale=1, use_cuda=False, noise=None, return_logits=False, offset=None,
+                          num_samples=1):
     channels = y.size(2)
     elbo, log_p, kl, y_hat, logits = _core("galaxy", x, y, p_net, q_net, rotate, translate, dx_scale, theta_prior,
-                                           z_scale, None, None, noise, use_cuda, augment_rotation, offset)
-    out = (elbo, log_p, kl, y_hat.view(y.size(0), -1, channels))
+                                           z_scale, None, None, noise, use_cuda, augment_rotation, offset, num_samples)
+    out = (elbo, log_p, kl, y_hat.view(y.size(0) * num_samples, -1, channels))
     return out + (logits,) if return_logits else out
 
 
 def eval_minibatch_particles(x, y, mask, ctf, p_net, q_net, rotate=True, translate=True, dx_scale=0.1,
                              theta_prior=math.pi, augment_rotation=False, z_scale=1, use_cuda=False, noise=None,
-                             return_logits=False, offset=None):
+                             return_logits=False, offset=None, num_samples=1):
     elbo, log_p, kl, y_hat, logits = _core("particles", x, y, p_net, q_net, rotate, translate, dx_scale, theta_prior,
-                                           z_scale, mask, ctf, noise, use_cuda, augment_rotation, offset)
+                                           z_scale, mask, ctf, noise, use_cuda, augment_rotation, offset, num_samples)
     out = (elbo, log_p, kl)
     return out + (logits,) if return_logits else out
 

@@ -304,6 +304,108 @@ def elbo_head(loglik, kl_b):
     return _ElboHead.apply(loglik, kl_b)
 
 
+def _check_samples(K):
+    K = int(K)
+    if not 1 <= K <= _lib.IW_MAX_SAMPLES:
+        raise RuntimeError("num_samples must be in [1, %d], got %d" % (_lib.IW_MAX_SAMPLES, K))
+    return K
+
+
+class _LatentIW(torch.autograd.Function):
+    """theta, dx, z_content, log_ratio = latent_head_iw(q_out, r, K): K draws per image from one encoder output, row b*K + k
+    is sample k of image b (svae_latent_iw_forward/backward)."""
+
+    @staticmethod
+    def forward(ctx, q_out, r, K, rotate, translate, mu_penalty, dx_scale, z_scale, theta_prior):
+        L = _lib.lib()
+        _require_hip(q_out, "encoder output")
+        _require_hip(r, "noise")
+        K = _check_samples(K)
+        q_out, r = _f32(q_out), _f32(r)
+        rows, inf = r.shape
+        B = q_out.shape[0]
+        if rows != B * K or q_out.shape != (B, 2 * inf):
+            raise RuntimeError("latent_head_iw: q_out %s and r %s do not describe %d samples per image"
+                               % (tuple(q_out.shape), tuple(r.shape), K))
+        d = _lib.LatentDesc(B, inf, int(bool(rotate)), int(bool(translate)), int(bool(mu_penalty)), float(dx_scale),
+                            float(z_scale), float(theta_prior))
+        dev = q_out.device
+        zd = inf - (1 if rotate else 0) - (2 if translate else 0)
+        theta = torch.empty(rows, dtype=torch.float32, device=dev) if rotate else None
+        dx = torch.empty(rows, 2, dtype=torch.float32, device=dev) if translate else None
+        zc = torch.empty(rows, zd, dtype=torch.float32, device=dev)
+        log_ratio = torch.empty(rows, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.svae_latent_iw_forward(ctypes.byref(d), K, q_out.data_ptr(), r.data_ptr(), _p(theta), _p(dx),
+                                                zc.data_ptr() if zd > 0 else None, log_ratio.data_ptr(), _stream(dev)))
+        ctx.desc, ctx.K, ctx.q_out, ctx.r = d, K, q_out, r
+        ctx.set_materialize_grads(False)
+        return theta, dx, zc, log_ratio
+
+    @staticmethod
+    def backward(ctx, g_theta, g_dx, g_zc, g_lr):
+        L = _lib.lib()
+        q_out, r = ctx.q_out, ctx.r
+        g_theta, g_dx, g_zc, g_lr = _f32(g_theta), _f32(g_dx), _f32(g_zc), _f32(g_lr)
+        if g_zc is not None and g_zc.numel() == 0:
+            g_zc = None
+        gq = torch.empty_like(q_out)
+        with torch.cuda.device(q_out.device):
+            _lib.check(L.svae_latent_iw_backward(ctypes.byref(ctx.desc), ctx.K, q_out.data_ptr(), r.data_ptr(), _p(g_theta),
+                                                 _p(g_dx), _p(g_zc), _p(g_lr), gq.data_ptr(), _stream(q_out.device)))
+        return gq, None, None, None, None, None, None, None, None
+
+
+def latent_head_iw(q_out, r, K, rotate, translate, mu_penalty, dx_scale, z_scale, theta_prior):
+    """(theta | None, dx | None, z_content, log p(z) - log q(z|x)) for K samples per image: q_out (B, 2*inf_dim) is the encoder
+    output [z_mu | z_logstd], r (B*K, inf_dim) the noise; every output has B*K rows, sample k of image b in row b*K + k."""
+    return _LatentIW.apply(q_out, r, K, rotate, translate, mu_penalty, dx_scale, z_scale, theta_prior)
+
+
+class _IWHead(torch.autograd.Function):
+    """bound, log_p, kl = mean_b log mean_k exp(loglik + log_ratio), mean(loglik), mean(-log_ratio)
+    (svae_iw_head_forward/backward)."""
+
+    @staticmethod
+    def forward(ctx, loglik, log_ratio, K):
+        L = _lib.lib()
+        _require_hip(loglik, "loglik")
+        _require_hip(log_ratio, "log_ratio")
+        K = _check_samples(K)
+        loglik, log_ratio = _f32(loglik), _f32(log_ratio)
+        rows = loglik.numel()
+        if log_ratio.numel() != rows or rows % K or rows == 0:
+            raise RuntimeError("iw_head: loglik has %d entries, log_ratio %d, for %d samples per image"
+                               % (rows, log_ratio.numel(), K))
+        ctx.set_materialize_grads(False)
+        out = torch.empty(3, dtype=torch.float32, device=loglik.device)
+        weights = torch.empty(rows, dtype=torch.float32, device=loglik.device)
+        with torch.cuda.device(loglik.device):
+            _lib.check(L.svae_iw_head_forward(loglik.data_ptr(), log_ratio.data_ptr(), rows // K, K, out.data_ptr(),
+                                              weights.data_ptr(), _stream(loglik.device)))
+        ctx.B, ctx.K, ctx.shapes = rows // K, K, (loglik.shape, log_ratio.shape)
+        ctx.save_for_backward(weights)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, g_bound, g_logp, g_kl):
+        L = _lib.lib()
+        weights, = ctx.saved_tensors
+        g_bound, g_logp, g_kl = _f32(g_bound), _f32(g_logp), _f32(g_kl)
+        dl = torch.empty_like(weights)
+        dr = torch.empty_like(weights)
+        with torch.cuda.device(weights.device):
+            _lib.check(L.svae_iw_head_backward(_p(g_bound), _p(g_logp), _p(g_kl), weights.data_ptr(), ctx.B, ctx.K,
+                                               dl.data_ptr(), dr.data_ptr(), _stream(weights.device)))
+        return dl.view(ctx.shapes[0]), dr.view(ctx.shapes[1]), None
+
+
+def iw_head(loglik, log_ratio, K):
+    """(bound, log_p_x_g_z, kl_div) of a minibatch from the per-sample log-likelihoods and log p(z) - log q(z|x), each (B*K):
+    three views of one vector, like elbo_head.  For K >= 2 the bound is not log_p - kl."""
+    return _IWHead.apply(loglik, log_ratio, K)
+
+
 ENC_ACT = {None: -1, "tanh": 0, "leakyrelu": 1, "relu": 2, "sigmoid": 3}
 ENC_LINEAR_MAX_WEIGHT = 4 * 1024 * 1024     # elements: the hand-written layer is for weights of a few MB (see svae.h)
 

@@ -54,7 +54,21 @@ def mnist_arguments(argv=None):
     p.add_argument("--skip_nonfinite", action="store_true",
                    help="skip the Adam update of a step whose gradient norm is NaN or inf: parameters, moments and the step count "
                         "stay as they are (default: off -- the reference applies it)")
-    return p.parse_args(argv)
+    p.add_argument("--num_samples", type=int, default=1, metavar="K",
+                   help="train on the K-sample importance-weighted bound log((1/K) sum_k p(x|z_k) p(z_k) / q(z_k|x)) instead of "
+                        "the one-sample ELBO (1 <= K <= 1024; default 1 = the reference's objective).  For K >= 2 the table's "
+                        "columns are the bound, the mean log p(x|z) and a Monte-Carlo estimate of the KL: the first is no "
+                        "longer the second minus the third")
+    p.add_argument("--eval_num_samples", type=int, default=None, metavar="K",
+                   help="samples per image in the validation passes (default: the value of --num_samples); train with a small K, "
+                        "compare models with a large one")
+    args = p.parse_args(argv)
+    if args.eval_num_samples is None:
+        args.eval_num_samples = args.num_samples
+    for name in ("num_samples", "eval_num_samples"):
+        if not 1 <= getattr(args, name) <= 1024:
+            p.error("%s must be in [1, 1024]" % name)
+    return args
 
 
 def dataset_files(dataset):
