@@ -2,8 +2,9 @@
 train_particles.py at the repository root).
 
 The reference triplicates its loop per script (train_mnist.py:127-226 and 268-469, train_galaxy.py:186-294
-and 346-575, train_particles.py:151-245 and 272-547); here ONE loop serves all three and the scripts only
-declare their flag surfaces (which differ: underscores for mnist/galaxy, hyphens for particles).  Kept:
+and 346-575, train_particles.py:151-245 and 272-547); here ONE loop serves all three.  Each script declares
+only the reference's flag surface (underscores for mnist/galaxy, hyphens for particles); the options this build adds are
+declared once, in add_shared_options, and what the loop does differently per script is one record in SCRIPTS.  Kept:
 flag names and defaults, the step order (loss = -elbo; backward; step; zero_grad), the running-mean metric
 arithmetic, the stdout tables, train.txt / val.txt / command.txt / models.txt, and the whole-module
 `.sav` checkpoints with the reference's file names.  Dropped (out of scope): the
@@ -14,6 +15,7 @@ archive and dataset download.  `--augment_rotation` runs on the device
 `--progress_every` (the reference pays three .item() syncs per step for its progress line), and `--num_samples K` /
 `--eval_num_samples K` (the K-sample importance-weighted bound for the training / validation passes; 1 = the reference).
 """
+import collections
 import copy
 import math
 import os
@@ -125,13 +127,85 @@ def eval_pass_plan(ntest, bs, inf_dim, device, home=None, display_shapes=(), num
     return tb, noise, shown
 
 
+# What the one loop does differently for each of the three scripts; train_main(script, ...) looks its record up by name.
+Script = collections.namedtuple("Script", [
+    "eval_fn",              # name of the elbo.eval_minibatch_* function (looked up on the module when train_main runs)
+    "mask_ctf",             # minibatches are (y, mask, ctf), not (y,)
+    "z_schedule",           # z_scale = 0 for the first --z_delay epochs, 1 after them
+    "augment",              # --augment_rotation applies (to training steps)
+    "run_dir",              # owns outputs_<prefix>/: command.txt, models.txt, train.txt / val.txt, the sample PNG (and the
+                            # loader draw in front of it), the final .sav files under trained/
+    "dumps",                # PNGs of a save-interval epoch besides the reconstruction: "dis" draws (B, inf_dim), "rnd" (B, z_dim)
+    "split_rows",           # table: two 1-based `Epoch / Split` rows per epoch, not a 0-based training and a validation line
+    "prefix_required",      # --save_prefix is mandatory
+    "save_interval_free",   # a resumed run may change --save_interval (it draws nothing: no image dump)
+    "activations",          # (--activation names -> module class, the class of every other name)
+])
+SCRIPTS = {
+    # 'relu' means LeakyReLU in mnist/particles (train_mnist.py:344-348, train_particles.py:433-436) but nn.ReLU in galaxy,
+    # where 'leakyrelu' is mis-spelt in the reference and silently gives Tanh (train_galaxy.py:426-434)
+    "mnist": Script(eval_fn="eval_minibatch_mnist", mask_ctf=False, z_schedule=False, augment=False, run_dir=True,
+                    dumps=("dis",), split_rows=False, prefix_required=True, save_interval_free=False,
+                    activations=({"tanh": nn.Tanh}, nn.LeakyReLU)),
+    "galaxy": Script(eval_fn="eval_minibatch_galaxy", mask_ctf=False, z_schedule=True, augment=True, run_dir=True,
+                     dumps=("dis", "rnd"), split_rows=False, prefix_required=True, save_interval_free=False,
+                     activations=({"tanh": nn.Tanh, "relu": nn.ReLU, "sigmoid": nn.Sigmoid}, nn.Tanh)),
+    "particles": Script(eval_fn="eval_minibatch_particles", mask_ctf=True, z_schedule=True, augment=True, run_dir=False,
+                        dumps=(), split_rows=True, prefix_required=False, save_interval_free=True,
+                        activations=({"tanh": nn.Tanh}, nn.LeakyReLU)),
+}
+
+
 def activation_class(script, name):
-    """The scripts' (inconsistent) flag-to-module maps: 'relu' means LeakyReLU in mnist/particles
-    (train_mnist.py:344-348, train_particles.py:433-436) but nn.ReLU in galaxy, where 'leakyrelu' is
-    mis-spelt in the reference and silently gives Tanh (train_galaxy.py:426-434)."""
-    if script == "galaxy":
-        return {"tanh": nn.Tanh, "relu": nn.ReLU, "sigmoid": nn.Sigmoid}.get(name, nn.Tanh)
-    return nn.Tanh if name == "tanh" else nn.LeakyReLU
+    """The scripts' (inconsistent) flag-to-module maps."""
+    named, other = SCRIPTS[script].activations
+    return named.get(name, other)
+
+
+def add_shared_options(p, sep, synthetic_help):
+    """The options this build adds to the reference's flag surfaces, the same for the three scripts up to the separator inside
+    their names (`sep`: "_" for mnist and galaxy, "-" for particles) and the --synthetic help text."""
+    def o(name):
+        return "--" + name.replace("_", sep)
+
+    p.add_argument("--synthetic", type=int, default=0, help=synthetic_help)
+    p.add_argument(o("progress_every"), type=int, default=50, help="stderr progress line every N steps (0 = never)")
+    p.add_argument("--seed", type=int, default=None,
+                   help="seed torch and numpy before the networks are built (the reference has no such flag: unseeded by default)")
+    p.add_argument("--gemm", choices=["fp32", "fp16x3"], default=None,
+                   help="hidden-layer GEMM path (default: SVAE_GEMM or fp32 MFMA; fp16x3 = fp32-accurate split-operand f16 MFMA)")
+    p.add_argument("--resume", default=None, metavar="PATH",
+                   help="continue from this training state file (written by {}) with the same arguments; only {} "
+                        "may grow.  Under the world size that wrote it the run continues bit for bit; another world size is "
+                        "accepted but changes the summation order, as it does for a fresh run".format(
+                            o("checkpoint_interval"), o("num_epochs")))
+    p.add_argument(o("checkpoint_interval"), type=int, default=0, metavar="N",
+                   help="write <prefix>_state_epoch<NN>.ckpt (parameters, Adam moments, step count, generator states, table rows) "
+                        "beside the .sav files after every N-th epoch and after the last one (0 = never)")
+    p.add_argument(o("clip_grad_norm"), type=float, default=None, metavar="X",
+                   help="clip the global L2 norm of the gradient at X before every Adam update (the arithmetic of "
+                        "torch.nn.utils.clip_grad_norm_, on the device; default: off -- the reference does not clip)")
+    p.add_argument(o("skip_nonfinite"), action="store_true",
+                   help="skip the Adam update of a step whose gradient norm is NaN or inf: parameters, moments and the step count "
+                        "stay as they are (default: off -- the reference applies it)")
+    p.add_argument(o("num_samples"), type=int, default=1, metavar="K",
+                   help="train on the K-sample importance-weighted bound log((1/K) sum_k p(x|z_k) p(z_k) / q(z_k|x)) instead of "
+                        "the one-sample ELBO (1 <= K <= 1024; default 1 = the reference's objective).  For K >= 2 the table's "
+                        "columns are the bound, the mean log p(x|z) and a Monte-Carlo estimate of the KL: the first is no "
+                        "longer the second minus the third")
+    p.add_argument(o("eval_num_samples"), type=int, default=None, metavar="K",
+                   help="samples per image in the validation passes (default: the value of {}); train with a small K, "
+                        "compare models with a large one".format(o("num_samples")))
+
+
+def finish_options(p, args):
+    """--eval_num_samples defaults to --num_samples; both are sample counts the kernels take."""
+    if args.eval_num_samples is None:
+        args.eval_num_samples = args.num_samples
+    for name in ("num_samples", "eval_num_samples"):
+        if not 1 <= getattr(args, name) <= 1024:
+            p.error("%s must be in [1, 1024]" % name)
+    return args
 
 
 def pick_device(d, world=1, local=0):
@@ -249,10 +323,16 @@ def plain_args(args):
     return out
 
 
-def dataset_fingerprint(y_train, y_test):
-    """The float64 sums the loop already forms to check that data-parallel ranks hold one dataset, plus the shapes."""
-    return {"sums": torch.stack([y_train.double().sum(), y_test.double().sum()]).cpu(),
-            "train_shape": [int(d) for d in y_train.shape], "test_shape": [int(d) for d in y_test.shape]}
+def dataset_sums(y_train, y_test):
+    """The float64 sums by which data-parallel ranks check that they hold one dataset, and a resumed run that it holds the
+    stored run's."""
+    return torch.stack([y_train.double().sum(), y_test.double().sum()])
+
+
+def dataset_fingerprint(y_train, y_test, sums=None):
+    """dataset_sums (`sums`, where the caller has formed them already) plus the shapes."""
+    sums = dataset_sums(y_train, y_test) if sums is None else sums
+    return {"sums": sums.cpu(), "train_shape": [int(d) for d in y_train.shape], "test_shape": [int(d) for d in y_test.shape]}
 
 
 def checkpoint_path(path_prefix, epoch_str):
@@ -300,8 +380,8 @@ def check_resume_args(ck, args, script):
     one that has nothing left to do.  Every rank reads the same file and the same arguments, so all refuse alike."""
     now = plain_args(args)
     free = set(RESUME_FREE_ARGS)
-    if script == "particles":
-        free.add("save_interval")           # particles dumps no images: the interval only decides when .sav files are written
+    if SCRIPTS[script].save_interval_free:
+        free.add("save_interval")           # no images are dumped: the interval only decides when .sav files are written
     # a file written before the gradient guard / the sample counts existed: both guard options off, one sample per image
     stored = dict(RESUME_ARG_DEFAULTS, **ck["args"])
     now = dict(RESUME_ARG_DEFAULTS, **now)
@@ -330,14 +410,6 @@ def check_resume_fingerprint(ck, fingerprint):
             b.tolist(), a.tolist()))
 
 
-def _metric_vector(out):
-    """(elbo, log_p, kl) of an eval_minibatch result as one 3-vector (ops.elbo_head returns views of one)."""
-    base = getattr(out[0], "_base", None)
-    if base is not None and base.numel() == 3:
-        return base.detach()
-    return torch.stack([out[0].detach(), out[1].detach(), out[2].detach()])
-
-
 def _take(t, sel, device):
     """Rows `sel` of a dataset tensor on `device`: a gather in HBM when the dataset is resident there (the default, as the
     reference preloads: train_mnist.py:329-332), a host gather + one asynchronous upload under --no-preload."""
@@ -347,28 +419,33 @@ def _take(t, sel, device):
     return (rows.pin_memory() if device.type == "cuda" else rows).to(device, non_blocking=True)
 
 
-def run_epoch(script, step, x, batches, train, N, epoch, num_epochs, rank, world, progress_every, extra):
+def run_epoch(script, step, x, batches, train, *, data, inf_dim, noise=None, mask=None, kw=None, train_kw=None, dump=None,
+              num_samples=1, epoch=0, num_epochs=1, rank=0, world=1, progress_every=0):
     """One pass over `batches` (a list of index tensors into the resident data; every rank holds the same list).
     Training uses dp.TrainStep (forward, backward, all-reduce, Adam); evaluation only the forward (it is stochastic in
     the reference too: eval_model draws noise, train_mnist.py:174-226).
 
+    data: {"y": images, "ctf": filters or None}, indexed by `batches`; mask: the particles' pixel mask.  noise: one prepared
+    (gb*K, inf_dim) draw per minibatch (pass_noise), else each is drawn here.  kw: keywords of every eval_minibatch call of
+    the pass (z_scale); train_kw: those of training steps only (augment_rotation).  dump(y, y_hat): called on rank 0 with the
+    first minibatch (the image files of a save-interval epoch).  epoch, num_epochs, progress_every: the progress line only.
+
     Data parallel: rank g works on rows [lo, hi) of each GLOBAL minibatch.  The N(0,1) draw is made for the whole
-    global minibatch from a generator every rank seeded identically (extra["noise_gen"]) and sliced like the data, and
+    global minibatch from the generator every rank seeded identically and sliced like the data, and
     so are the augmentation angles, so a G-rank step computes what the 1-rank step computes (up to fp32 summation
     order).  Training metrics come back inside the gradient all-reduce (step.metrics); evaluation metrics are
     collected per batch and all-reduced ONCE per epoch.  A rank with an empty slice (ragged last batch smaller than the
     world) contributes zeros.
 
-    extra["num_samples"] = K >= 2: the pass evaluates the K-sample importance-weighted bound.  Shards stay by image; the
+    num_samples = K >= 2: the pass evaluates the K-sample importance-weighted bound.  Shards stay by image; the
     noise of a global minibatch is (gb*K, inf_dim) and rank g takes rows [lo*K, hi*K)."""
+    rule = SCRIPTS[script]
     p_net, q_net = step.p_net, step.q_net
-    K = int(extra.get("num_samples", 1))
+    K = int(num_samples)
     p_net.train(train)
     q_net.train(train)
-    data = extra["data"]
-    mean = RunningMean(x.device)
-    inf_dim = extra["inf_dim"]
-    noise_list = extra.get("noise")
+    mean = RunningMean()
+    total = sum(idx.numel() for idx in batches)     # images of the pass, for the progress line
     pending = []
     for it, idx in enumerate(batches):
         gb = idx.numel()
@@ -376,23 +453,23 @@ def run_epoch(script, step, x, batches, train, N, epoch, num_epochs, rank, world
         sel = idx[lo:hi]
         y = _take(data["y"], sel, x.device)
         args = (y,)
-        if script == "particles":
+        if rule.mask_ctf:
             ctf = _take(data["ctf"], sel, x.device) if data.get("ctf") is not None else None
-            args = (y, extra.get("mask"), ctf)
-        kw = dict(extra.get("kw", {}))
-        if noise_list is not None:
-            r = noise_list[it]
+            args = (y, mask, ctf)
+        call_kw = dict(kw or {})
+        if noise is not None:
+            r = noise[it]
         else:       # no prepared draws: the reference's per-minibatch draw from the global CPU generator (train_mnist.py:38)
             r = torch.empty(gb * K, inf_dim).normal_().to(x.device, non_blocking=True)
-        kw["noise"] = r[lo * K:hi * K]
+        call_kw["noise"] = r[lo * K:hi * K]
         if K > 1:
-            kw["num_samples"] = K
+            call_kw["num_samples"] = K
         out = None
         if train:
-            kw.update(extra.get("train_kw", {}))        # augmentation applies to training steps only (train_galaxy.py:204)
-            if world > 1 and kw.get("augment_rotation") and step.eval_kwargs.get("rotate"):
-                kw["offset"] = E.draw_offsets(step.eval_kwargs["rotate"], gb)[lo:hi]   # np.random is seeded alike on all ranks
-            out = step(x, *args, weight=(hi - lo) / gb, global_batch=gb, **kw)
+            call_kw.update(train_kw or {})              # augmentation applies to training steps only (train_galaxy.py:204)
+            if world > 1 and call_kw.get("augment_rotation") and step.eval_kwargs.get("rotate"):
+                call_kw["offset"] = E.draw_offsets(step.eval_kwargs["rotate"], gb)[lo:hi]   # np.random is seeded alike on all ranks
+            out = step(x, *args, weight=(hi - lo) / gb, global_batch=gb, **call_kw)
             # the data-parallel metric tail (also the one-rank RCCL rehearsal, and any weight != 1) is overwritten by the
             # next step: keep a copy of it, not a reference
             mean.update(gb, step.metrics, volatile=step.metrics is step.grads.tail)
@@ -400,21 +477,19 @@ def run_epoch(script, step, x, batches, train, N, epoch, num_epochs, rank, world
             vals = torch.zeros(3, device=x.device)
             if hi > lo:
                 with torch.no_grad():
-                    call = dict(step.eval_kwargs)
-                    call.update(kw)
-                    out = step.eval_minibatch(x, *args, p_net, q_net, **call)
-                vals = _metric_vector(out)
+                    out = step.eval_minibatch(x, *args, p_net, q_net, **dict(step.eval_kwargs, **call_kw))
+                vals = dp.metric_vector(out)
             if world > 1:
                 pending.append((gb, vals * ((hi - lo) / gb)))
             else:
                 mean.update(gb, vals)
-        if it == 0 and extra.get("dump") and rank == 0 and out is not None:   # first batch of a save-interval epoch (train_mnist.py:214-224)
+        if it == 0 and dump and rank == 0 and out is not None:   # first batch of a save-interval epoch (train_mnist.py:214-224)
             # the posed reconstruction shown is each image's first sample
-            extra["dump"](y, (out[3] if K == 1 else out[3][::K]) if len(out) > 3 else None)
+            dump(y, (out[3] if K == 1 else out[3][::K]) if len(out) > 3 else None)
         if train and rank == 0 and progress_every > 0 and (it + 1) % progress_every == 0:
             e, g, k = mean.values()
             print("# [{}/{}] training {:.1%}, ELBO={:.5f}, Error={:.5f}, KL={:.5f}".format(
-                epoch + 1, num_epochs, mean.seen / N, e, g, k), end="\r", file=sys.stderr)
+                epoch + 1, num_epochs, mean.seen / total, e, g, k), end="\r", file=sys.stderr)
     if pending:
         allv = torch.stack([v for _, v in pending])
         torch.distributed.all_reduce(allv)
@@ -428,25 +503,24 @@ def run_epoch(script, step, x, batches, train, N, epoch, num_epochs, rank, world
 def train_main(script, args, build):
     """`build(args, device)` returns dict(y_train, y_test, ctf_train, ctf_test, mask, n, m, channels,
     p_net, q_net, rotate, translate, table)."""
+    rule = SCRIPTS[script]
     rank, world, local = dp.init_process_group(device_is_gpu=True)
     device = pick_device(args.device, world, local)
     # --resume: every rank opens the file itself and checks it against its own (identical) arguments before the first
     # collective, so a rank that cannot read it -- or a run that does not match -- ends here and not inside a broadcast
     resume = None
-    if getattr(args, "resume", None):
+    if args.resume:
         resume = read_checkpoint(args.resume)
         check_resume_args(resume, args, script)
-    ckpt_every = getattr(args, "checkpoint_interval", 0) or 0
+    ckpt_every = args.checkpoint_interval
     if ckpt_every < 0:
         raise SystemExit("the checkpoint interval must be >= 0")
-    if ckpt_every and script == "particles" and args.save_prefix is None:
+    if ckpt_every and not rule.prefix_required and args.save_prefix is None:
         raise SystemExit("--checkpoint-interval needs --save-prefix (the state files are written beside the .sav files)")
-    clip = getattr(args, "clip_grad_norm", None)
-    skip_nonfinite = bool(getattr(args, "skip_nonfinite", False))
+    clip = args.clip_grad_norm
     if clip is not None and not clip > 0:
         raise SystemExit("the gradient-norm threshold must be > 0")
-    train_k = int(getattr(args, "num_samples", 1) or 1)
-    eval_k = int(getattr(args, "eval_num_samples", None) or train_k)
+    train_k, eval_k = args.num_samples, args.eval_num_samples
     # Randomness is consumed from torch's GLOBAL CPU generator and np.random in the order the reference's main() consumes
     # them (SURVEY.md A.6): default initialisation of p_net then q_net, one draw for the sample-image pass over the validation
     # loader, then per epoch the two draws of iter(DataLoader(shuffle=True)), one N(0,1) draw per training minibatch, one draw
@@ -455,23 +529,22 @@ def train_main(script, args, build):
     # trajectory of the reference's CPU path under the same seed.  Under data-parallel execution every rank seeds alike
     # (--seed, else rank 0's seed), makes the same draws and slices [lo:hi) of each global minibatch; np.random (the dataset
     # shuffle of train_galaxy.py:372 inside build(), the augmentation angles) is seeded alike too.
-    seed = getattr(args, "seed", None)
+    seed = args.seed
     if seed is None and world > 1:
         seed = dp.shared_seed(device)
     if seed is not None:
         torch.manual_seed(seed)
         np.random.seed(seed % (2 ** 32))
-    if getattr(args, "gemm", None):                 # before the first decoder call: buffer sizes depend on the mode
+    if args.gemm:                                   # before the first decoder call: buffer sizes depend on the mode
         from . import _lib
         _lib.set_gemm_mode(args.gemm)
     start = time.time()
     prefix = args.save_prefix
     out_dir = trained = None
-    if script != "particles":
-        if prefix is None:
-            raise SystemExit("--save_prefix is required (the reference crashes without it: src/misc_tools.py:22)")
-        if rank == 0:
-            out_dir, trained = make_run_dir(prefix, args)
+    if rule.prefix_required and prefix is None:
+        raise SystemExit("--save_prefix is required (the reference crashes without it: src/misc_tools.py:22)")
+    if rule.run_dir and rank == 0:
+        out_dir, trained = make_run_dir(prefix, args)
     cfg = build(args, device)
     p_net, q_net = cfg["p_net"].to(device), cfg["q_net"].to(device)
     if rank == 0 and out_dir:
@@ -487,30 +560,32 @@ def train_main(script, args, build):
     mask = cfg.get("mask")
     mask = mask.to(device) if mask is not None else None
     N = tr["y"].size(0)
-    fingerprint = None
+    sums = fingerprint = None
+    if resume is not None or ckpt_every or world > 1:
+        sums = dataset_sums(tr["y"], te["y"])
     if resume is not None or ckpt_every:
-        fingerprint = dataset_fingerprint(tr["y"], te["y"])
+        fingerprint = dataset_fingerprint(tr["y"], te["y"], sums)
         if resume is not None:
             check_resume_fingerprint(resume, fingerprint)
-    fn = {"mnist": E.eval_minibatch_mnist, "galaxy": E.eval_minibatch_galaxy, "particles": E.eval_minibatch_particles}[script]
-    step = dp.TrainStep(p_net, q_net, fn, lr=args.learning_rate, rotate=cfg["rotate"], translate=cfg["translate"],
-                        dx_scale=args.dx_scale, theta_prior=args.theta_prior, clip_grad_norm=clip, skip_nonfinite=skip_nonfinite)
+    step = dp.TrainStep(p_net, q_net, getattr(E, rule.eval_fn), lr=args.learning_rate, rotate=cfg["rotate"],
+                        translate=cfg["translate"], dx_scale=args.dx_scale, theta_prior=args.theta_prior, clip_grad_norm=clip,
+                        skip_nonfinite=args.skip_nonfinite)
     print("# using priors: theta={}, dx={}".format(args.theta_prior, args.dx_scale), file=sys.stderr)
     num_epochs = args.num_epochs
     digits = int(math.log10(num_epochs)) + 1
     bs = args.minibatch_size
     if world > 1:       # every rank must hold the SAME dataset: the ranks slice one global minibatch by index
-        dp.assert_same_on_all_ranks(torch.stack([tr["y"].double().sum(), te["y"].double().sum()]).to(device), "the dataset")
+        dp.assert_same_on_all_ranks(sums.to(device), "the dataset")
     inf_dim = q_net.latent_dim
     out = sys.stdout
     header = cfg["table"]
     if rank == 0:
         print("\t".join(header), file=out)
     train_lines, val_lines = ["\t".join(header)], ["\t".join(header)]
-    z_delay = getattr(args, "z_delay", 0)
+    z_delay = getattr(args, "z_delay", 0)               # mnist has no such option
     label = save_label(args) if out_dir else None
     ntest = te["y"].size(0)
-    if script != "particles":                                        # MiscTools.sample_images: one pass is started over the
+    if rule.run_dir:                                                 # MiscTools.sample_images: one pass is started over the
         loader_order(ntest, False)                                   # validation loader (train_mnist.py:402) -> one draw
         if out_dir:
             export_batch_as_image(te["y"][:bs], "{}/images/_sample_{}.png".format(out_dir, label), [cfg["n"], cfg["m"]])
@@ -532,16 +607,15 @@ def train_main(script, args, build):
         set_rng_state(resume["rng"])
     state_prefix = None
     if ckpt_every and rank == 0:
-        state_prefix = prefix if script == "particles" else os.path.join(trained, prefix)
+        state_prefix = os.path.join(trained, prefix) if rule.run_dir else prefix
     for epoch in range(first_epoch, num_epochs):
-        kw = {}
-        if script != "mnist":
-            kw["z_scale"] = 0 if epoch < z_delay else 1
+        kw = {"z_scale": 0 if epoch < z_delay else 1} if rule.z_schedule else {}
         batches, noise = train_pass_plan(N, bs, inf_dim, device, home, train_k)    # same order and draws on every rank
-        train_kw = {"augment_rotation": True} if cfg.get("augment") and script != "mnist" else {}
+        train_kw = {"augment_rotation": True} if cfg.get("augment") and rule.augment else {}
         t_epoch = time.time()
-        e, g, k = run_epoch(script, step, x, batches, True, N, epoch, num_epochs, rank, world, args.progress_every,
-                            dict(data=tr, mask=mask, kw=kw, train_kw=train_kw, inf_dim=inf_dim, noise=noise, num_samples=train_k))
+        e, g, k = run_epoch(script, step, x, batches, True, data=tr, inf_dim=inf_dim, noise=noise, mask=mask, kw=kw,
+                            train_kw=train_kw, num_samples=train_k, epoch=epoch, num_epochs=num_epochs, rank=rank, world=world,
+                            progress_every=args.progress_every)
         if rank == 0:       # run_epoch's values() synchronised: the epoch's training pass is complete
             print("# epoch {}: {} training images in {:.3f} s = {:.0f} images/s".format(
                 epoch + 1, N, time.time() - t_epoch, N / max(time.time() - t_epoch, 1e-9)), file=sys.stderr)
@@ -552,16 +626,16 @@ def train_main(script, args, build):
                     gs["mean_norm"], gs["max_norm"], gs["clipped"], gs["steps"], gs["skipped"]), file=sys.stderr)
         dump = None
         shapes = None
-        if script != "particles" and (epoch + 1) % args.save_interval == 0:
+        if rule.dumps and (epoch + 1) % args.save_interval == 0:
             # the display helpers' draws are made on every rank (one random stream), the files written by rank 0
             shapes = display_draw_shapes(script, inf_dim, args.z_dim)
         tb, noise, shown = eval_pass_plan(ntest, bs, inf_dim, device, home, shapes, eval_k)
         if shapes and out_dir:
             dump = _image_dumper(script, step, x, cfg, out_dir, str(epoch + 1).zfill(digits), label, kw, args.z_dim, shown)
-        ev = run_epoch(script, step, x, tb, False, ntest, epoch, num_epochs, rank, world, 0,
-                       dict(data=te, mask=mask, kw=kw, dump=dump, inf_dim=inf_dim, noise=noise, num_samples=eval_k))
+        ev = run_epoch(script, step, x, tb, False, data=te, inf_dim=inf_dim, noise=noise, mask=mask, kw=kw, dump=dump,
+                       num_samples=eval_k, rank=rank, world=world)
         if rank == 0:
-            if script == "particles":
+            if rule.split_rows:
                 rows.append("\t".join([str(epoch + 1), "train", str(e), str(g), str(k)]))
                 rows.append("\t".join([str(epoch + 1), "test", str(ev[0]), str(ev[1]), str(ev[2])]))
                 print(rows[-2], file=out)
@@ -574,12 +648,12 @@ def train_main(script, args, build):
                 val_lines.append(line)
                 print(line, file=out)
             out.flush()
-            if script == "particles" and prefix is not None and (epoch + 1) % args.save_interval == 0:
+            if not rule.run_dir and prefix is not None and (epoch + 1) % args.save_interval == 0:
                 save_models(prefix, str(epoch + 1).zfill(digits), p_net, q_net, device)
             if state_prefix is not None and ((epoch + 1) % ckpt_every == 0 or epoch + 1 == num_epochs):
                 write_checkpoint(checkpoint_path(state_prefix, str(epoch + 1).zfill(digits)), step.state_dict(), epoch + 1,
                                  args, world, fingerprint, dict(train_lines=train_lines, val_lines=val_lines, rows=rows))
-    if rank == 0 and script != "particles":
+    if rank == 0 and rule.run_dir:
         save_models(os.path.join(trained, prefix), str(num_epochs).zfill(digits), p_net, q_net, device)
         with open(os.path.join(out_dir, "train.txt"), "w") as f:
             print("\n".join(train_lines), file=f)
@@ -595,15 +669,15 @@ def display_draw_shapes(script, inf_dim, z_dim):
     """Shapes of the N(0,1) draws eval_model's image dump makes for a first minibatch of B images: minibatch_for_display
     draws (B, inf_dim) (train_mnist.py:107, train_galaxy.py:146); galaxy's random_minibatch_generator then (B, z_dim)
     (train_galaxy.py:177)."""
-    if script == "galaxy":
-        return lambda B: [(B, inf_dim), (B, z_dim)]
-    return lambda B: [(B, inf_dim)]
+    width = {"dis": inf_dim, "rnd": z_dim}
+    return lambda B: [(B, width[d]) for d in SCRIPTS[script].dumps]
 
 
 def _image_dumper(script, step, x, cfg, out_dir, epoch_str, label, kw, z_dim, shown=(None, None)):
     """The PNG dumps of eval_model (train_mnist.py:214-224, train_galaxy.py:275-292): <epoch>_dis_ = decoded from the
     content latents on the unposed grid, <epoch>_ = the posed reconstruction y_hat of the same batch, galaxy also
     <epoch>_rnd_ = decoded prior samples.  `shown`: the helpers' N(0,1) draws, made by pass_noise in the reference's order."""
+    rule = SCRIPTS[script]
     dims = [cfg["n"], cfg["m"]]
     p_net, q_net = step.p_net, step.q_net
     shown = list(shown) + [None, None]
@@ -613,12 +687,13 @@ def _image_dumper(script, step, x, cfg, out_dir, epoch_str, label, kw, z_dim, sh
         rows = y.size(0)                        # data parallel: rank 0's slice [0, rows) of the first global minibatch
         shown[0] = shown[0][:rows] if shown[0] is not None else None
         shown[1] = shown[1][:rows] if shown[1] is not None else None
-        if script == "mnist":
+        zs = kw.get("z_scale", 1)
+        if not rule.z_schedule:
             dis = E.minibatch_for_display(x, y, p_net, q_net, rotate=cfg["rotate"], translate=cfg["translate"], noise=shown[0])
         else:
-            zs = kw.get("z_scale", 1)
             dis = E.minibatch_for_display_galaxy(x, y, q_net, p_net, rotate=cfg["rotate"], translate=cfg["translate"], z_scale=zs,
                                                  noise=shown[0])
+        if "rnd" in rule.dumps:
             rnd = E.random_minibatch_generator(x, y, p_net, z_dim, z_scale=zs, noise=shown[1])
             export_batch_as_image(rnd, "{}_rnd_{}.png".format(base, label), dims)
         export_batch_as_image(dis, "{}_dis_{}.png".format(base, label), dims)

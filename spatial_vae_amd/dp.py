@@ -233,6 +233,15 @@ def shared_seed(device):
     return seed
 
 
+def metric_vector(out):
+    """(elbo, log_p, kl) of an eval_minibatch result as one detached 3-vector.  ops.elbo_head returns three views of one
+    such vector, which is handed back itself (no copy, no kernel); any other result is stacked."""
+    base = getattr(out[0], "_base", None)
+    if base is not None and base.numel() == 3:
+        return base.detach()
+    return torch.stack([out[0].detach(), out[1].detach(), out[2].detach()])
+
+
 def assert_same_on_all_ranks(t, what):
     """Raise on every rank if the values of `t` (a small tensor) differ between ranks."""
     if not collectives_on():
@@ -626,12 +635,11 @@ class TrainStep(object):
             elbo = out[0]
             # loss = -elbo (train_mnist.py:147-148) without a negation kernel; under DP the seed is -local/global
             elbo.backward(self._seed(weight))
-            base = getattr(elbo, "_base", None)           # ops.elbo_head returns views of one (elbo, log_p, kl) vector
-            vec = base if (base is not None and base.numel() == 3) else torch.stack([out[0], out[1], out[2]])
+            vec = metric_vector(out)
             if not collectives_on() and weight == 1.0:
-                self.metrics = vec.detach()               # nothing to reduce: the minibatch's own metrics, no copy
+                self.metrics = vec                        # nothing to reduce: the minibatch's own metrics, no copy
             else:
-                torch.mul(vec.detach(), float(weight), out=self.grads.tail)
+                torch.mul(vec, float(weight), out=self.grads.tail)
                 self.metrics = self.grads.tail
         else:
             self.grads.tail.zero_()

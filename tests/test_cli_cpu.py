@@ -50,6 +50,35 @@ def test_particles_flag_surface_uses_hyphens():
     assert abs(a.theta_prior - np.pi) < 1e-12 and a.scale == 1
 
 
+def test_parsers_reproduce_the_snapshot_taken_before_the_shared_options_moved():
+    """tests/golden/cli_args_snapshot.json: for each argv, the ordered (key, value) pairs of vars(args) as the three parsers
+    gave them at the commit the file names, before their shared options were declared once in cli.add_shared_options.  The
+    order matters: cli.save_label walks it, and cli.plain_args is what a state file stores."""
+    import json
+    import pytest
+    import train_galaxy
+    import train_mnist
+    import train_particles
+    parsers = {"mnist": train_mnist.mnist_arguments, "galaxy": train_galaxy.galaxy_arguments,
+               "particles": train_particles.particle_arguments}
+    with open(os.path.join(GOLDEN_DIR, "cli_args_snapshot.json")) as f:
+        cases = json.load(f)["cases"]
+    assert {c["script"] for c in cases} == set(parsers)
+    for c in cases:
+        got = [[k, v if isinstance(v, (bool, int, float, str, type(None))) else repr(v)]
+               for k, v in vars(parsers[c["script"]](c["argv"])).items()]
+        assert got == c["items"], (c["script"], c["argv"])
+        assert [type(v) for _, v in got] == [type(v) for _, v in c["items"]], (c["script"], c["argv"])   # 2 is not 2.0 here
+    # what the parent refused is still refused
+    minimal = {"mnist": [], "galaxy": ["tr.npy", "te.npy"], "particles": ["tr.npy", "te.npy"]}
+    for script, parse in parsers.items():
+        sep = "-" if script == "particles" else "_"
+        for bad in (["--num_samples", "0"], ["--eval_num_samples", "2000"], ["--gemm", "bf16"]):
+            with pytest.raises(SystemExit) as e:
+                parse(minimal[script] + [bad[0].replace("_", sep), bad[1]])
+            assert e.value.code == 2, (script, bad)
+
+
 def test_activation_maps_follow_the_scripts_quirks():
     import torch.nn as nn
     from spatial_vae_amd import cli

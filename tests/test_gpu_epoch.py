@@ -64,8 +64,8 @@ def test_run_epoch_matches_reference_train_epoch(name):
     for e, zs in enumerate(ec["z_scales"]):
         kw = {} if script == "mnist" else {"z_scale": zs}
         noise = [torch.from_numpy(r).to(dev) for r in inp["r"][e]]
-        means.append(cli.run_epoch(script, step, x, batches, True, int(bounds[-1]), e, len(ec["z_scales"]), 0, 1, 0,
-                                   dict(data=data, mask=mask, kw=kw, inf_dim=C.inf_dim(case), noise=noise)))
+        means.append(cli.run_epoch(script, step, x, batches, True, data=data, inf_dim=C.inf_dim(case), noise=noise, mask=mask,
+                                   kw=kw, epoch=e, num_epochs=len(ec["z_scales"])))
     got = np.array(per_step)
     assert got.shape == gold["steps"].shape
     assert np.abs(got - gold["steps"]).max() <= TOL_STEP * np.abs(gold["steps"]).max(), (got, gold["steps"])
@@ -80,8 +80,7 @@ def test_run_epoch_matches_reference_train_epoch(name):
     # the parameters agree with the reference's to 1e-4, so do the metrics
     kw = {} if script == "mnist" else {"z_scale": ec["z_scales"][-1]}
     noise = [torch.from_numpy(r).to(dev) for r in inp["r_eval"]]
-    ev = cli.run_epoch(script, step, x, batches, False, int(bounds[-1]), 0, 1, 0, 1, 0,
-                       dict(data=data, mask=mask, kw=kw, inf_dim=C.inf_dim(case), noise=noise))
+    ev = cli.run_epoch(script, step, x, batches, False, data=data, inf_dim=C.inf_dim(case), noise=noise, mask=mask, kw=kw)
     assert np.abs(np.array(ev) - gold["eval_means"]).max() <= 1e-4 * np.abs(gold["eval_means"]).max(), (ev, gold["eval_means"])
     assert not p_net.training and not q_net.training                       # eval_model leaves the networks in eval mode
 

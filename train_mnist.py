@@ -34,41 +34,8 @@ def mnist_arguments(argv=None):
     p.add_argument("-d", "--device", type=int, default=-2)
     p.add_argument("--num_train_images", type=int, default=0)      # parsed and unused, as in the reference
     p.add_argument("--val_split", type=int, default=50)            # parsed and unused, as in the reference
-    # additions
-    p.add_argument("--synthetic", type=int, default=0, help="train on this many synthetic 28x28 images (no data files)")
-    p.add_argument("--progress_every", type=int, default=50, help="stderr progress line every N steps (0 = never)")
-    p.add_argument("--seed", type=int, default=None,
-                   help="seed torch and numpy before the networks are built (the reference has no such flag: unseeded by default)")
-    p.add_argument("--gemm", choices=["fp32", "fp16x3"], default=None,
-                   help="hidden-layer GEMM path (default: SVAE_GEMM or fp32 MFMA; fp16x3 = fp32-accurate split-operand f16 MFMA)")
-    p.add_argument("--resume", default=None, metavar="PATH",
-                   help="continue from this training state file (written by --checkpoint_interval) with the same arguments; only --num_epochs "
-                        "may grow.  Under the world size that wrote it the run continues bit for bit; another world size is "
-                        "accepted but changes the summation order, as it does for a fresh run")
-    p.add_argument("--checkpoint_interval", type=int, default=0, metavar="N",
-                   help="write <prefix>_state_epoch<NN>.ckpt (parameters, Adam moments, step count, generator states, table rows) "
-                        "beside the .sav files after every N-th epoch and after the last one (0 = never)")
-    p.add_argument("--clip_grad_norm", type=float, default=None, metavar="X",
-                   help="clip the global L2 norm of the gradient at X before every Adam update (the arithmetic of "
-                        "torch.nn.utils.clip_grad_norm_, on the device; default: off -- the reference does not clip)")
-    p.add_argument("--skip_nonfinite", action="store_true",
-                   help="skip the Adam update of a step whose gradient norm is NaN or inf: parameters, moments and the step count "
-                        "stay as they are (default: off -- the reference applies it)")
-    p.add_argument("--num_samples", type=int, default=1, metavar="K",
-                   help="train on the K-sample importance-weighted bound log((1/K) sum_k p(x|z_k) p(z_k) / q(z_k|x)) instead of "
-                        "the one-sample ELBO (1 <= K <= 1024; default 1 = the reference's objective).  For K >= 2 the table's "
-                        "columns are the bound, the mean log p(x|z) and a Monte-Carlo estimate of the KL: the first is no "
-                        "longer the second minus the third")
-    p.add_argument("--eval_num_samples", type=int, default=None, metavar="K",
-                   help="samples per image in the validation passes (default: the value of --num_samples); train with a small K, "
-                        "compare models with a large one")
-    args = p.parse_args(argv)
-    if args.eval_num_samples is None:
-        args.eval_num_samples = args.num_samples
-    for name in ("num_samples", "eval_num_samples"):
-        if not 1 <= getattr(args, name) <= 1024:
-            p.error("%s must be in [1, 1024]" % name)
-    return args
+    cli.add_shared_options(p, "_", "train on this many synthetic 28x28 images (no data files)")
+    return cli.finish_options(p, p.parse_args(argv))
 
 
 def dataset_files(dataset):
