@@ -9,25 +9,105 @@ import torch  # noqa: F401
 
 from .build import library_path
 
-MAX_HIDDEN = 7
-ACT = {"tanh": 0, "leakyrelu": 1, "relu": 2, "sigmoid": 3}
-FLAG_RESID, FLAG_BILINEAR, FLAG_SOFTPLUS = 1, 2, 4
-
+# ---- the constants of include/svae.h (SVAE_ prefix dropped) ----
+# Every upper-case integer of this module is one of the header's #defines or enumerators and nothing else is:
+# tests/test_binding_cpu.py compares the two sets and their values.
 ABI_VERSION = 2
-IW_MAX_SAMPLES = 1024       # SVAE_IW_MAX_SAMPLES
+MAX_HIDDEN = 7
+MAX_OUT = 4
+IW_MAX_SAMPLES = 1024
+LINEAR_ACT_NONE = -1
+PROF_KINDS = 20             # length of the arrays svae_profile_read writes
+PATH_KINDS = 16             # length of the array svae_path_counts writes
+OK, E_INVALID, E_WORKSPACE, E_LAUNCH = 0, -1, -2, -3
+ACT_TANH, ACT_LEAKYRELU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3
+FLAG_RESID, FLAG_BILINEAR, FLAG_SOFTPLUS = 1, 2, 4
+GEMM_FP32, GEMM_FP16X3 = 0, 1
+
+ACT = {"tanh": ACT_TANH, "leakyrelu": ACT_LEAKYRELU, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID}
+GEMM_MODE = {"fp32": GEMM_FP32, "fp16x3": GEMM_FP16X3}
+
+vp, sz, cint, cstr = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p
+i32, i64, f32, f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
+ptr = ctypes.POINTER
 
 
-# every function include/svae.h declares; build() and tests/test_host_cpu.py re-derive this list from the header and check it
-# against the library's exports (the header is documentation: importing the package must not need it)
-EXPORTS = ("svae_abi_version", "svae_adam_step", "svae_adam_step_guarded", "svae_bce_loglik", "svae_colsum", "svae_ctf_filter",
-           "svae_ctf_filter_workspace_bytes", "svae_decoder_backward", "svae_decoder_forward",
-           "svae_decoder_forward_bce", "svae_elbo_head_backward", "svae_elbo_head_forward", "svae_gaussian_loglik",
-           "svae_gaussian_workspace_bytes", "svae_gemm_mode_get", "svae_gemm_mode_set", "svae_grad_guard_control_bytes",
-           "svae_grad_guard_norm", "svae_grad_guard_workspace_bytes", "svae_iw_head_backward", "svae_iw_head_forward",
-           "svae_last_error", "svae_latent_backward", "svae_latent_forward", "svae_latent_iw_backward",
-           "svae_latent_iw_forward", "svae_linear_backward", "svae_linear_forward",
-           "svae_path_counts", "svae_path_name", "svae_profile_enable", "svae_profile_kind_name",
-           "svae_profile_read", "svae_rotate_bicubic", "svae_saved_bytes", "svae_workspace_bytes")
+# ---- the structs of include/svae.h (device pointers are c_void_p: the callers hold addresses, not ctypes objects) ----
+class Desc(ctypes.Structure):
+    _fields_ = [(n, i32) for n in ("B", "N", "H", "L", "Zd", "C", "in_dim", "act", "flags")]
+
+
+class Params(ctypes.Structure):
+    _fields_ = [("coord_w", vp), ("coord_b", vp), ("latent_w", vp), ("bilinear_w", vp), ("hidden_w", vp * MAX_HIDDEN),
+                ("hidden_b", vp * MAX_HIDDEN), ("out_w", vp), ("out_b", vp)]
+
+
+Grads = Params      # svae_grads: svae_params' fields without the const (the test holds the header to that)
+
+
+class Pose(ctypes.Structure):
+    _fields_ = [("coords", vp), ("grid", vp), ("theta", vp), ("dx", vp)]
+
+
+class PoseGrads(ctypes.Structure):
+    _fields_ = [("dcoords", vp), ("dtheta", vp), ("ddx", vp)]
+
+
+class LatentDesc(ctypes.Structure):
+    _fields_ = [("B", i32), ("inf_dim", i32), ("rotate", i32), ("translate", i32), ("mu_penalty", i32), ("dx_scale", f32),
+                ("z_scale", f32), ("theta_prior", f32)]
+
+
+class GuardControl(ctypes.Structure):
+    """svae_guard_control: all zero bytes = a fresh record; the statistics are the bytes from `steps` to the end."""
+    _fields_ = [("t", i64), ("total", f32), ("coef", f32), ("step_size", f32), ("sqrt_bc2", f32), ("apply", i32),
+                ("finite", i32), ("steps", i64), ("clipped", i64), ("skipped", i64), ("norm_sum", f64), ("norm_max", f32),
+                ("reserved", f32)]
+
+
+# ---- every function include/svae.h declares: name -> (return type, argument types) ----
+# The one declaration of the binding: lib() applies it, EXPORTS is its keys, and tests/test_binding_cpu.py parses the header's
+# prototypes and holds each row to them, type by type (the header is documentation: importing the package must not need it).
+SIGNATURES = {
+    "svae_abi_version": (cint, []),
+    "svae_last_error": (cstr, []),
+    "svae_saved_bytes": (sz, [ptr(Desc)]),
+    "svae_workspace_bytes": (sz, [ptr(Desc)]),
+    "svae_decoder_forward": (cint, [ptr(Desc), ptr(Params), ptr(Pose), vp, vp, vp, vp, vp, sz, vp]),
+    "svae_decoder_forward_bce": (cint, [ptr(Desc), ptr(Params), ptr(Pose), vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "svae_decoder_backward": (cint, [ptr(Desc), ptr(Params), ptr(Pose), vp, vp, vp, vp, vp, ptr(Grads), vp, ptr(PoseGrads),
+                                     vp, sz, vp]),
+    "svae_bce_loglik": (cint, [i32, i32, vp, vp, vp, vp, vp]),
+    "svae_gaussian_workspace_bytes": (sz, [i32, i32]),
+    "svae_gaussian_loglik": (cint, [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]),
+    "svae_latent_forward": (cint, [ptr(LatentDesc), vp, vp, vp, vp, vp, vp, vp]),
+    "svae_latent_backward": (cint, [ptr(LatentDesc), vp, vp, vp, vp, vp, vp, vp, vp]),
+    "svae_elbo_head_forward": (cint, [vp, vp, i32, vp, vp]),
+    "svae_elbo_head_backward": (cint, [vp, vp, vp, i32, vp, vp, vp]),
+    "svae_latent_iw_forward": (cint, [ptr(LatentDesc), i32, vp, vp, vp, vp, vp, vp, vp]),
+    "svae_latent_iw_backward": (cint, [ptr(LatentDesc), i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "svae_iw_head_forward": (cint, [vp, vp, i32, i32, vp, vp, vp]),
+    "svae_iw_head_backward": (cint, [vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "svae_colsum": (cint, [vp, i32, i32, vp, vp]),
+    "svae_linear_forward": (cint, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "svae_linear_backward": (cint, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "svae_adam_step": (cint, [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, i32, vp]),
+    "svae_grad_guard_control_bytes": (sz, []),
+    "svae_grad_guard_workspace_bytes": (sz, [i64]),
+    "svae_grad_guard_norm": (cint, [vp, i64, f32, f32, f32, f32, vp, vp, sz, vp]),
+    "svae_adam_step_guarded": (cint, [vp, vp, vp, vp, i64, f32, f32, f32, i32, vp, vp]),
+    "svae_rotate_bicubic": (cint, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "svae_ctf_filter_workspace_bytes": (sz, [i32, i32, i32]),
+    "svae_ctf_filter": (cint, [vp, vp, i32, i32, i32, f64, vp, sz, vp]),
+    "svae_gemm_mode_set": (cint, [cint]),
+    "svae_gemm_mode_get": (cint, []),
+    "svae_profile_enable": (cint, [cint]),
+    "svae_profile_read": (cint, [ptr(f64), ptr(i64)]),
+    "svae_profile_kind_name": (cstr, [cint]),
+    "svae_path_counts": (cint, [ptr(i64), cint]),
+    "svae_path_name": (cstr, [cint]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 def declared_in_header(header=None):
@@ -36,42 +116,6 @@ def declared_in_header(header=None):
     header = header or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "svae.h")
     with open(header) as f:
         return tuple(sorted(set(re.findall(r"\b(svae_[a-z0-9_]+)\s*\(", f.read()))))
-
-
-PROF_KINDS = 20
-
-
-class Desc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("B", "N", "H", "L", "Zd", "C", "in_dim", "act", "flags")]
-
-
-class Params(ctypes.Structure):
-    _fields_ = [("coord_w", ctypes.c_void_p), ("coord_b", ctypes.c_void_p), ("latent_w", ctypes.c_void_p),
-                ("bilinear_w", ctypes.c_void_p), ("hidden_w", ctypes.c_void_p * MAX_HIDDEN),
-                ("hidden_b", ctypes.c_void_p * MAX_HIDDEN), ("out_w", ctypes.c_void_p), ("out_b", ctypes.c_void_p)]
-
-
-class Pose(ctypes.Structure):
-    _fields_ = [("coords", ctypes.c_void_p), ("grid", ctypes.c_void_p), ("theta", ctypes.c_void_p),
-                ("dx", ctypes.c_void_p)]
-
-
-class LatentDesc(ctypes.Structure):
-    _fields_ = [("B", ctypes.c_int32), ("inf_dim", ctypes.c_int32), ("rotate", ctypes.c_int32),
-                ("translate", ctypes.c_int32), ("mu_penalty", ctypes.c_int32), ("dx_scale", ctypes.c_float),
-                ("z_scale", ctypes.c_float), ("theta_prior", ctypes.c_float)]
-
-
-class GuardControl(ctypes.Structure):
-    """svae_guard_control: all zero bytes = a fresh record; the statistics are the bytes from `steps` to the end."""
-    _fields_ = [("t", ctypes.c_int64), ("total", ctypes.c_float), ("coef", ctypes.c_float), ("step_size", ctypes.c_float),
-                ("sqrt_bc2", ctypes.c_float), ("apply", ctypes.c_int32), ("finite", ctypes.c_int32), ("steps", ctypes.c_int64),
-                ("clipped", ctypes.c_int64), ("skipped", ctypes.c_int64), ("norm_sum", ctypes.c_double),
-                ("norm_max", ctypes.c_float), ("reserved", ctypes.c_float)]
-
-
-class PoseGrads(ctypes.Structure):
-    _fields_ = [("dcoords", ctypes.c_void_p), ("dtheta", ctypes.c_void_p), ("ddx", ctypes.c_void_p)]
 
 
 _lib = None
@@ -87,83 +131,9 @@ def lib():
         raise RuntimeError("spatial_vae_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
-    vp, sz, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32
-    L.svae_abi_version.restype = ctypes.c_int
-    L.svae_last_error.restype = ctypes.c_char_p
-    L.svae_saved_bytes.restype = sz
-    L.svae_saved_bytes.argtypes = [ctypes.POINTER(Desc)]
-    L.svae_workspace_bytes.restype = sz
-    L.svae_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
-    L.svae_decoder_forward.restype = ctypes.c_int
-    L.svae_decoder_forward.argtypes = [ctypes.POINTER(Desc), ctypes.POINTER(Params), ctypes.POINTER(Pose), vp,
-                                       vp, vp, vp, vp, sz, vp]
-    L.svae_decoder_forward_bce.restype = ctypes.c_int
-    L.svae_decoder_forward_bce.argtypes = [ctypes.POINTER(Desc), ctypes.POINTER(Params), ctypes.POINTER(Pose), vp,
-                                           vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.svae_decoder_backward.restype = ctypes.c_int
-    L.svae_decoder_backward.argtypes = [ctypes.POINTER(Desc), ctypes.POINTER(Params), ctypes.POINTER(Pose), vp,
-                                        vp, vp, vp, vp, ctypes.POINTER(Params), vp, ctypes.POINTER(PoseGrads),
-                                        vp, sz, vp]
-    L.svae_bce_loglik.restype = ctypes.c_int
-    L.svae_bce_loglik.argtypes = [i32, i32, vp, vp, vp, vp, vp]
-    L.svae_gaussian_workspace_bytes.restype = sz
-    L.svae_gaussian_workspace_bytes.argtypes = [i32, i32]
-    L.svae_gaussian_loglik.restype = ctypes.c_int
-    L.svae_gaussian_loglik.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]
-    L.svae_latent_forward.restype = ctypes.c_int
-    L.svae_latent_forward.argtypes = [ctypes.POINTER(LatentDesc), vp, vp, vp, vp, vp, vp, vp]
-    L.svae_latent_backward.restype = ctypes.c_int
-    L.svae_latent_backward.argtypes = [ctypes.POINTER(LatentDesc), vp, vp, vp, vp, vp, vp, vp, vp]
-    L.svae_elbo_head_forward.restype = ctypes.c_int
-    L.svae_elbo_head_forward.argtypes = [vp, vp, i32, vp, vp]
-    L.svae_elbo_head_backward.restype = ctypes.c_int
-    L.svae_elbo_head_backward.argtypes = [vp, vp, vp, i32, vp, vp, vp]
-    L.svae_latent_iw_forward.restype = ctypes.c_int
-    L.svae_latent_iw_forward.argtypes = [ctypes.POINTER(LatentDesc), i32, vp, vp, vp, vp, vp, vp, vp]
-    L.svae_latent_iw_backward.restype = ctypes.c_int
-    L.svae_latent_iw_backward.argtypes = [ctypes.POINTER(LatentDesc), i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.svae_iw_head_forward.restype = ctypes.c_int
-    L.svae_iw_head_forward.argtypes = [vp, vp, i32, i32, vp, vp, vp]
-    L.svae_iw_head_backward.restype = ctypes.c_int
-    L.svae_iw_head_backward.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
-    L.svae_colsum.restype = ctypes.c_int
-    L.svae_colsum.argtypes = [vp, i32, i32, vp, vp]
-    L.svae_linear_forward.restype = ctypes.c_int
-    L.svae_linear_forward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.svae_linear_backward.restype = ctypes.c_int
-    L.svae_linear_backward.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.svae_adam_step.restype = ctypes.c_int
-    L.svae_adam_step.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                 ctypes.c_float, ctypes.c_int64, i32, vp]
-    L.svae_grad_guard_control_bytes.restype = sz
-    L.svae_grad_guard_control_bytes.argtypes = []
-    L.svae_grad_guard_workspace_bytes.restype = sz
-    L.svae_grad_guard_workspace_bytes.argtypes = [ctypes.c_int64]
-    L.svae_grad_guard_norm.restype = ctypes.c_int
-    L.svae_grad_guard_norm.argtypes = [vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                       vp, vp, sz, vp]
-    L.svae_adam_step_guarded.restype = ctypes.c_int
-    L.svae_adam_step_guarded.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, i32,
-                                         vp, vp]
-    L.svae_rotate_bicubic.restype = ctypes.c_int
-    L.svae_rotate_bicubic.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
-    L.svae_ctf_filter.restype = ctypes.c_int
-    L.svae_ctf_filter_workspace_bytes.restype = sz
-    L.svae_ctf_filter_workspace_bytes.argtypes = [i32, i32, i32]
-    L.svae_ctf_filter.argtypes = [vp, vp, i32, i32, i32, ctypes.c_double, vp, sz, vp]
-    L.svae_gemm_mode_set.restype = ctypes.c_int
-    L.svae_gemm_mode_set.argtypes = [ctypes.c_int]
-    L.svae_gemm_mode_get.restype = ctypes.c_int
-    L.svae_profile_enable.restype = ctypes.c_int
-    L.svae_profile_enable.argtypes = [ctypes.c_int]
-    L.svae_profile_read.restype = ctypes.c_int
-    L.svae_profile_read.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
-    L.svae_profile_kind_name.restype = ctypes.c_char_p
-    L.svae_profile_kind_name.argtypes = [ctypes.c_int]
-    L.svae_path_counts.restype = ctypes.c_int
-    L.svae_path_counts.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
-    L.svae_path_name.restype = ctypes.c_char_p
-    L.svae_path_name.argtypes = [ctypes.c_int]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:
         raise RuntimeError("spatial_vae_amd: %s has ABI version %d, this binding needs %d -- rebuild it"
                            % (path, L.svae_abi_version(), ABI_VERSION))
@@ -182,11 +152,12 @@ def check(rc):
 def set_gemm_mode(name):
     """'fp32' (fp32 MFMA) or 'fp16x3' (split-operand f16 MFMA, fp32-accurate).  Call before any decoder call of the process:
     buffer sizes depend on it."""
-    check(lib().svae_gemm_mode_set({"fp32": 0, "fp16x3": 1}[name]))
+    check(lib().svae_gemm_mode_set(GEMM_MODE[name]))
 
 
 def gemm_mode():
-    return ("fp32", "fp16x3")[lib().svae_gemm_mode_get()]
+    mode = lib().svae_gemm_mode_get()
+    return next(name for name, code in GEMM_MODE.items() if code == mode)
 
 
 def profile_enable(level):
@@ -201,9 +172,6 @@ def profile_read():
     cnt = (ctypes.c_int64 * PROF_KINDS)()
     check(L.svae_profile_read(ms, cnt))
     return {L.svae_profile_kind_name(k).decode(): (ms[k], cnt[k]) for k in range(PROF_KINDS) if cnt[k]}
-
-
-PATH_KINDS = 16
 
 
 def path_counts(reset=False):

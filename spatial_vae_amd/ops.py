@@ -48,8 +48,27 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+# per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
+_POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
+                 for name, (_, argtypes) in _lib.SIGNATURES.items()}
+
+
+def _call(name, device, *args):
+    """Run the status-returning entry point `name` of include/svae.h on `device` and its current stream (the header's last
+    argument, appended here).  Where the header takes a device pointer the argument is a tensor, handed over as its data_ptr(),
+    or None for NULL; numbers and ctypes.byref(...) pass as they are.  Nothing is converted or copied: a tensor must already
+    have the dtype and the contiguous layout the header asks for."""
+    argv = list(args)
+    for i in _POINTER_ARGS[name]:
+        t = argv[i]
+        if t is not None:
+            if not t.is_contiguous():
+                raise RuntimeError("spatial_vae_amd: %s was handed a non-contiguous tensor of shape %s, strides %s"
+                                   % (name, tuple(t.shape), t.stride()))
+            argv[i] = t.data_ptr()
+    fn = getattr(_lib.lib(), name)
+    with torch.cuda.device(device):
+        _lib.check(fn(*argv, torch.cuda.current_stream(device).cuda_stream))
 
 
 def make_desc(spec, B, N):
@@ -116,21 +135,18 @@ class _Decoder(torch.autograd.Function):
         y = torch.empty((B, N, spec.n_out), dtype=torch.float32, device=device)
         logits = torch.empty_like(y)
         loglik = dll = None
-        with torch.cuda.device(device):
-            if target is None:
-                _lib.check(L.svae_decoder_forward(ctypes.byref(desc), ctypes.byref(params), ctypes.byref(pose), _p(z),
-                                                  y.data_ptr(), logits.data_ptr(), _p(saved), ws.data_ptr(), ws.numel(),
-                                                  _stream(device)))
-            else:
-                target = _f32(target)
-                _require_hip(target, "target")
-                if target.numel() != y.numel():
-                    raise RuntimeError("target shape %s does not match the decoder output %s" % (tuple(target.shape), tuple(y.shape)))
-                loglik = torch.empty(B, dtype=torch.float32, device=device)
-                dll = torch.empty_like(y) if need_grad else None
-                _lib.check(L.svae_decoder_forward_bce(ctypes.byref(desc), ctypes.byref(params), ctypes.byref(pose), _p(z),
-                                                      target.data_ptr(), y.data_ptr(), logits.data_ptr(), loglik.data_ptr(),
-                                                      _p(dll), _p(saved), ws.data_ptr(), ws.numel(), _stream(device)))
+        if target is None:
+            _call("svae_decoder_forward", device, ctypes.byref(desc), ctypes.byref(params), ctypes.byref(pose), z, y, logits,
+                  saved, ws, ws.numel())
+        else:
+            target = _f32(target)
+            _require_hip(target, "target")
+            if target.numel() != y.numel():
+                raise RuntimeError("target shape %s does not match the decoder output %s" % (tuple(target.shape), tuple(y.shape)))
+            loglik = torch.empty(B, dtype=torch.float32, device=device)
+            dll = torch.empty_like(y) if need_grad else None
+            _call("svae_decoder_forward_bce", device, ctypes.byref(desc), ctypes.byref(params), ctypes.byref(pose), z, target,
+                  y, logits, loglik, dll, saved, ws, ws.numel())
         ctx.spec, ctx.B, ctx.N = spec, B, N
         ctx.sinks = sinks
         # everything the backward call reads goes through save_for_backward, so the buffers have the lifetime the reference's
@@ -189,16 +205,13 @@ class _Decoder(torch.autograd.Function):
         g_bw = new(bilinear_w, ng[8] and bil, "bilinear_w")
         g_ow, g_ob = new(out_w, ng[9], "out_w"), new(out_b, ng[10], "out_b")
         g_hidden = tuple(new(h, ng[11 + i], "hidden%d" % i) for i, h in enumerate(hidden))
-        grads = _fill_params(_lib.Params(), g_cw, g_cb, g_lw, g_bw, g_ow, g_ob, g_hidden)
+        grads = _fill_params(_lib.Grads(), g_cw, g_cb, g_lw, g_bw, g_ow, g_ob, g_hidden)
         pg = _lib.PoseGrads()
         pg.dcoords, pg.dtheta, pg.ddx = _p(g_coords), _p(g_theta), _p(g_dx)
         ws_bytes = L.svae_workspace_bytes(ctypes.byref(desc))
         ws = _buf(device, ws_bytes, "ws")
-        with torch.cuda.device(device):
-            _lib.check(L.svae_decoder_backward(ctypes.byref(desc), ctypes.byref(params), ctypes.byref(pose), _p(z),
-                                               logits.data_ptr(), dy.data_ptr(), _p(dy_scale), saved_buf.data_ptr(),
-                                               ctypes.byref(grads), _p(g_z), ctypes.byref(pg), ws.data_ptr(), ws.numel(),
-                                               _stream(device)))
+        _call("svae_decoder_backward", device, ctypes.byref(desc), ctypes.byref(params), ctypes.byref(pose), z, logits, dy,
+              dy_scale, saved_buf, ctypes.byref(grads), g_z, ctypes.byref(pg), ws, ws.numel())
         ready = sinks.get("__ready__")   # dp.TrainStep: every decoder gradient is now enqueued -> start its all-reduce
         if ready is not None:
             ready()
@@ -229,7 +242,6 @@ class _Latent(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q_out, r, rotate, translate, mu_penalty, dx_scale, z_scale, theta_prior):
-        L = _lib.lib()
         _require_hip(q_out, "encoder output")
         q_out, r = _f32(q_out), _f32(r)
         B, inf = r.shape
@@ -243,23 +255,18 @@ class _Latent(torch.autograd.Function):
         dx = torch.empty(B, 2, dtype=torch.float32, device=dev) if translate else None
         zc = torch.empty(B, zd, dtype=torch.float32, device=dev)
         kl = torch.empty(B, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.svae_latent_forward(ctypes.byref(d), q_out.data_ptr(), r.data_ptr(), _p(theta), _p(dx),
-                                             zc.data_ptr() if zd > 0 else None, kl.data_ptr(), _stream(dev)))
+        _call("svae_latent_forward", dev, ctypes.byref(d), q_out, r, theta, dx, zc if zd > 0 else None, kl)
         ctx.desc, ctx.q_out, ctx.r = d, q_out, r
         return theta, dx, zc, kl
 
     @staticmethod
     def backward(ctx, g_theta, g_dx, g_zc, g_kl):
-        L = _lib.lib()
         q_out, r = ctx.q_out, ctx.r
         g_theta, g_dx, g_zc, g_kl = _f32(g_theta), _f32(g_dx), _f32(g_zc), _f32(g_kl)
         if g_zc is not None and g_zc.numel() == 0:
             g_zc = None
         gq = torch.empty_like(q_out)
-        with torch.cuda.device(q_out.device):
-            _lib.check(L.svae_latent_backward(ctypes.byref(ctx.desc), q_out.data_ptr(), r.data_ptr(), _p(g_theta), _p(g_dx),
-                                              _p(g_zc), _p(g_kl), gq.data_ptr(), _stream(q_out.device)))
+        _call("svae_latent_backward", q_out.device, ctypes.byref(ctx.desc), q_out, r, g_theta, g_dx, g_zc, g_kl, gq)
         return gq, None, None, None, None, None, None, None
 
 
@@ -273,7 +280,6 @@ class _ElboHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, loglik, kl_b):
-        L = _lib.lib()
         _require_hip(loglik, "loglik")
         loglik, kl_b = _f32(loglik), _f32(kl_b)
         B = loglik.numel()
@@ -281,21 +287,17 @@ class _ElboHead(torch.autograd.Function):
             raise RuntimeError("loglik has %d entries, kl %d" % (B, kl_b.numel()))
         ctx.set_materialize_grads(False)     # unused outputs (log_p, kl) arrive as None, not as zero tensors autograd fills
         out = torch.empty(3, dtype=torch.float32, device=loglik.device)
-        with torch.cuda.device(loglik.device):
-            _lib.check(L.svae_elbo_head_forward(loglik.data_ptr(), kl_b.data_ptr(), B, out.data_ptr(), _stream(loglik.device)))
+        _call("svae_elbo_head_forward", loglik.device, loglik, kl_b, B, out)
         ctx.B, ctx.shapes = B, (loglik.shape, kl_b.shape)
         return out[0], out[1], out[2]
 
     @staticmethod
     def backward(ctx, g_elbo, g_logp, g_kl):
-        L = _lib.lib()
         ref = next(g for g in (g_elbo, g_logp, g_kl) if g is not None)
         g_elbo, g_logp, g_kl = _f32(g_elbo), _f32(g_logp), _f32(g_kl)
         dl = torch.empty(ctx.B, dtype=torch.float32, device=ref.device)
         dk = torch.empty(ctx.B, dtype=torch.float32, device=ref.device)
-        with torch.cuda.device(ref.device):
-            _lib.check(L.svae_elbo_head_backward(_p(g_elbo), _p(g_logp), _p(g_kl), ctx.B, dl.data_ptr(), dk.data_ptr(),
-                                                 _stream(ref.device)))
+        _call("svae_elbo_head_backward", ref.device, g_elbo, g_logp, g_kl, ctx.B, dl, dk)
         return dl.view(ctx.shapes[0]), dk.view(ctx.shapes[1])
 
 
@@ -317,7 +319,6 @@ class _LatentIW(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q_out, r, K, rotate, translate, mu_penalty, dx_scale, z_scale, theta_prior):
-        L = _lib.lib()
         _require_hip(q_out, "encoder output")
         _require_hip(r, "noise")
         K = _check_samples(K)
@@ -335,24 +336,19 @@ class _LatentIW(torch.autograd.Function):
         dx = torch.empty(rows, 2, dtype=torch.float32, device=dev) if translate else None
         zc = torch.empty(rows, zd, dtype=torch.float32, device=dev)
         log_ratio = torch.empty(rows, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.svae_latent_iw_forward(ctypes.byref(d), K, q_out.data_ptr(), r.data_ptr(), _p(theta), _p(dx),
-                                                zc.data_ptr() if zd > 0 else None, log_ratio.data_ptr(), _stream(dev)))
+        _call("svae_latent_iw_forward", dev, ctypes.byref(d), K, q_out, r, theta, dx, zc if zd > 0 else None, log_ratio)
         ctx.desc, ctx.K, ctx.q_out, ctx.r = d, K, q_out, r
         ctx.set_materialize_grads(False)
         return theta, dx, zc, log_ratio
 
     @staticmethod
     def backward(ctx, g_theta, g_dx, g_zc, g_lr):
-        L = _lib.lib()
         q_out, r = ctx.q_out, ctx.r
         g_theta, g_dx, g_zc, g_lr = _f32(g_theta), _f32(g_dx), _f32(g_zc), _f32(g_lr)
         if g_zc is not None and g_zc.numel() == 0:
             g_zc = None
         gq = torch.empty_like(q_out)
-        with torch.cuda.device(q_out.device):
-            _lib.check(L.svae_latent_iw_backward(ctypes.byref(ctx.desc), ctx.K, q_out.data_ptr(), r.data_ptr(), _p(g_theta),
-                                                 _p(g_dx), _p(g_zc), _p(g_lr), gq.data_ptr(), _stream(q_out.device)))
+        _call("svae_latent_iw_backward", q_out.device, ctypes.byref(ctx.desc), ctx.K, q_out, r, g_theta, g_dx, g_zc, g_lr, gq)
         return gq, None, None, None, None, None, None, None, None
 
 
@@ -368,7 +364,6 @@ class _IWHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, loglik, log_ratio, K):
-        L = _lib.lib()
         _require_hip(loglik, "loglik")
         _require_hip(log_ratio, "log_ratio")
         K = _check_samples(K)
@@ -380,23 +375,18 @@ class _IWHead(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         out = torch.empty(3, dtype=torch.float32, device=loglik.device)
         weights = torch.empty(rows, dtype=torch.float32, device=loglik.device)
-        with torch.cuda.device(loglik.device):
-            _lib.check(L.svae_iw_head_forward(loglik.data_ptr(), log_ratio.data_ptr(), rows // K, K, out.data_ptr(),
-                                              weights.data_ptr(), _stream(loglik.device)))
+        _call("svae_iw_head_forward", loglik.device, loglik, log_ratio, rows // K, K, out, weights)
         ctx.B, ctx.K, ctx.shapes = rows // K, K, (loglik.shape, log_ratio.shape)
         ctx.save_for_backward(weights)
         return out[0], out[1], out[2]
 
     @staticmethod
     def backward(ctx, g_bound, g_logp, g_kl):
-        L = _lib.lib()
         weights, = ctx.saved_tensors
         g_bound, g_logp, g_kl = _f32(g_bound), _f32(g_logp), _f32(g_kl)
         dl = torch.empty_like(weights)
         dr = torch.empty_like(weights)
-        with torch.cuda.device(weights.device):
-            _lib.check(L.svae_iw_head_backward(_p(g_bound), _p(g_logp), _p(g_kl), weights.data_ptr(), ctx.B, ctx.K,
-                                               dl.data_ptr(), dr.data_ptr(), _stream(weights.device)))
+        _call("svae_iw_head_backward", weights.device, g_bound, g_logp, g_kl, weights, ctx.B, ctx.K, dl, dr)
         return dl.view(ctx.shapes[0]), dr.view(ctx.shapes[1]), None
 
 
@@ -406,7 +396,7 @@ def iw_head(loglik, log_ratio, K):
     return _IWHead.apply(loglik, log_ratio, K)
 
 
-ENC_ACT = {None: -1, "tanh": 0, "leakyrelu": 1, "relu": 2, "sigmoid": 3}
+ENC_ACT = {None: _lib.LINEAR_ACT_NONE, **_lib.ACT}
 ENC_LINEAR_MAX_WEIGHT = 4 * 1024 * 1024     # elements: the hand-written layer is for weights of a few MB (see svae.h)
 
 
@@ -424,14 +414,11 @@ class _EncLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, act, sink_w, sink_b):
-        L = _lib.lib()
         x, weight, bias = _f32(x), _f32(weight), _f32(bias)
         rows, k = x.shape
         n = weight.shape[0]
         out = torch.empty(rows, n, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.svae_linear_forward(x.data_ptr(), weight.data_ptr(), _p(bias), out.data_ptr(), rows, k, n, ENC_ACT[act],
-                                             _stream(x.device)))
+        _call("svae_linear_forward", x.device, x, weight, bias, out, rows, k, n, ENC_ACT[act])
         ctx.act = act
         ctx.sinks = (sink_w, sink_b)
         ctx.has_bias = bias is not None
@@ -440,7 +427,6 @@ class _EncLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        L = _lib.lib()
         x, weight, out = ctx.saved_tensors
         sink_w, sink_b = ctx.sinks
         dout = _f32(dout)
@@ -450,9 +436,7 @@ class _EncLinear(torch.autograd.Function):
         dx = torch.empty_like(x) if want_x else None
         dw = (sink_w if sink_w is not None else torch.empty_like(weight)) if want_w else None
         db = (sink_b if sink_b is not None else torch.empty(n, dtype=torch.float32, device=x.device)) if want_b else None
-        with torch.cuda.device(x.device):
-            _lib.check(L.svae_linear_backward(x.data_ptr(), weight.data_ptr(), out.data_ptr(), dout.data_ptr(), rows, k, n,
-                                              ENC_ACT[ctx.act], _p(dw), _p(db), _p(dx), _stream(x.device)))
+        _call("svae_linear_backward", x.device, x, weight, out, dout, rows, k, n, ENC_ACT[ctx.act], dw, db, dx)
         return (dx, None if (dw is None or dw is sink_w) else dw, None if (db is None or db is sink_b) else db, None, None, None)
 
 
@@ -487,8 +471,8 @@ class _SinkLinear(torch.autograd.Function):
             return dx, None, None, None, None, None, None
         torch.mm(dy.t(), x, out=sink_w)
         if dy.is_cuda and dy.dtype == torch.float32 and dy.is_contiguous() and sink_b.is_contiguous():
-            with torch.cuda.device(dy.device):   # column sums in ~3 us (ATen's reduce kernel takes 13 us for 256 x 500)
-                _lib.check(_lib.lib().svae_colsum(dy.data_ptr(), dy.size(0), dy.size(1), sink_b.data_ptr(), _stream(dy.device)))
+            # column sums in ~3 us (ATen's reduce kernel takes 13 us for 256 x 500)
+            _call("svae_colsum", dy.device, dy, dy.size(0), dy.size(1), sink_b)
         else:
             torch.sum(dy, 0, out=sink_b)
         return dx, None, None, None, None, None, None
@@ -503,7 +487,6 @@ class _BceLoglik(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y_hat, target):
-        L = _lib.lib()
         _require_hip(y_hat, "y_hat")
         y_hat, target = _f32(y_hat), _f32(target)
         B = y_hat.shape[0]
@@ -512,9 +495,7 @@ class _BceLoglik(torch.autograd.Function):
             raise RuntimeError("target shape %s does not match y_hat %s" % (tuple(target.shape), tuple(y_hat.shape)))
         loglik = torch.empty(B, dtype=torch.float32, device=y_hat.device)
         dll = torch.empty_like(y_hat) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(y_hat.device):
-            _lib.check(L.svae_bce_loglik(B, n, y_hat.data_ptr(), target.data_ptr(), loglik.data_ptr(), _p(dll),
-                                         _stream(y_hat.device)))
+        _call("svae_bce_loglik", y_hat.device, B, n, y_hat, target, loglik, dll)
         ctx.save_for_backward(dll)
         return loglik
 
@@ -545,9 +526,7 @@ class _GaussianLoglik(torch.autograd.Function):
         ws = _buf(y_params.device, ws_bytes, "gauss") if ws_bytes else None
         loglik = torch.empty(B, dtype=torch.float32, device=y_params.device)
         dll = torch.zeros_like(y_params) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(y_params.device):
-            _lib.check(L.svae_gaussian_loglik(B, N, C, y_params.data_ptr(), target.data_ptr(), _p(mask), _p(ctf), k,
-                                              loglik.data_ptr(), _p(dll), _p(ws), ws_bytes, _stream(y_params.device)))
+        _call("svae_gaussian_loglik", y_params.device, B, N, C, y_params, target, mask, ctf, k, loglik, dll, ws, ws_bytes)
         ctx.save_for_backward(dll)
         return loglik
 
@@ -598,9 +577,7 @@ def rotate_augment(y, offset, rows, cols, quantize_u8):
     mat_d = torch.from_numpy(mat).to(y.device, non_blocking=True)
     q_d = torch.from_numpy(quarter).to(y.device, non_blocking=True)
     out = torch.empty_like(yc)
-    with torch.cuda.device(y.device):
-        _lib.check(_lib.lib().svae_rotate_bicubic(yc.data_ptr(), out.data_ptr(), mat_d.data_ptr(), q_d.data_ptr(), B, rows,
-                                                  cols, C, 1 if quantize_u8 else 0, _stream(y.device)))
+    _call("svae_rotate_bicubic", y.device, yc, out, mat_d, q_d, B, rows, cols, C, 1 if quantize_u8 else 0)
     return out.view_as(y)
 
 
@@ -617,9 +594,7 @@ def ctf_filter(table, n, m, scale=1.0, device=None):
     L = _lib.lib()
     ws_bytes = L.svae_ctf_filter_workspace_bytes(tab.size(0), n, m)    # 0 while a filter's transform fits the LDS (~80 x 80)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    with torch.cuda.device(dev):
-        _lib.check(L.svae_ctf_filter(tab.data_ptr(), out.data_ptr(), tab.size(0), n, m, float(scale), _p(ws), ws_bytes,
-                                     _stream(dev)))
+    _call("svae_ctf_filter", dev, tab, out, tab.size(0), n, m, float(scale), ws, ws_bytes)
     return out
 
 
@@ -695,15 +670,11 @@ class FlatAdam(torch.optim.Optimizer):
                 if self.guarded:
                     ws_bytes = L.svae_grad_guard_workspace_bytes(p.numel())
                     ws = _buf(p.device, ws_bytes, "guard")
-                    with torch.cuda.device(p.device):
-                        _lib.check(L.svae_grad_guard_norm(p.grad.data_ptr(), p.numel(), self.max_grad_norm, group["lr"], b1, b2,
-                                                          st["guard"].data_ptr(), ws.data_ptr(), ws.numel(), _stream(p.device)))
-                        _lib.check(L.svae_adam_step_guarded(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
-                                                            st["exp_avg_sq"].data_ptr(), p.numel(), b1, b2, group["eps"], zero,
-                                                            st["guard"].data_ptr(), _stream(p.device)))
+                    _call("svae_grad_guard_norm", p.device, p.grad, p.numel(), self.max_grad_norm, group["lr"], b1, b2,
+                          st["guard"], ws, ws.numel())
+                    _call("svae_adam_step_guarded", p.device, p, p.grad, st["exp_avg"], st["exp_avg_sq"], p.numel(), b1, b2,
+                          group["eps"], zero, st["guard"])
                     continue
                 st["step"] += 1
-                with torch.cuda.device(p.device):
-                    _lib.check(L.svae_adam_step(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
-                                                st["exp_avg_sq"].data_ptr(), p.numel(), group["lr"], b1, b2, group["eps"],
-                                                st["step"], zero, _stream(p.device)))
+                _call("svae_adam_step", p.device, p, p.grad, st["exp_avg"], st["exp_avg_sq"], p.numel(), group["lr"], b1, b2,
+                      group["eps"], st["step"], zero)
