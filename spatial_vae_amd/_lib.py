@@ -109,9 +109,25 @@ SIGNATURES = {
 }
 EXPORTS = tuple(SIGNATURES)
 
+# ---- include/svae_stream.h: the streaming K-sample scorer, an addition with a header and a table of its own ----
+# Same rules as above (tests/test_stream_binding_cpu.py holds these rows to that header's prototypes); `state` is the address
+# of a record in device memory.  The header's one macro is iw_stream_cols below.
+STREAM_SIGNATURES = {
+    "svae_iw_stream_state_bytes": (sz, [i32, i32]),
+    "svae_iw_stream_reset": (cint, [vp, i32, i32, vp]),
+    "svae_iw_stream_update": (cint, [vp, ptr(LatentDesc), i32, vp, vp, vp, vp, vp, vp]),
+    "svae_iw_stream_finish": (cint, [vp, ptr(LatentDesc), vp, vp, vp]),
+}
+
+
+def iw_stream_cols(inf_dim):
+    """SVAE_IW_STREAM_COLS(inf_dim): floats per image in svae_iw_stream_finish's per_image."""
+    return 6 + 2 * int(inf_dim)
+
 
 def declared_in_header(header=None):
-    """The function names include/svae.h declares (used by build() and the tests, never at import)."""
+    """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
+    import)."""
     import re
     header = header or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "svae.h")
     with open(header) as f:
@@ -131,7 +147,7 @@ def lib():
         raise RuntimeError("spatial_vae_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

@@ -16,7 +16,8 @@ def _stale():
     if not os.path.exists(_LIB):
         return True
     t = os.path.getmtime(_LIB)
-    deps = [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(_HERE, "..", "include", "svae.h")]
+    deps = [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(_HERE, "..", "include", h)
+                                                         for h in ("svae.h", "svae_stream.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

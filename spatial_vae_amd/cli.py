@@ -711,3 +711,194 @@ def synthetic_images(kind, count, n, m, channels, seed):
     u = rs.uniform(size=shape)
     keep = rs.uniform(size=shape) > (0.8 if channels == 1 else 0.0)
     return np.floor(u * keep * 255.0).astype(np.float32)
+
+
+# ---- infer.py: apply a trained model to a dataset, one row per image --------------------------------------------------------
+INFER_MAX_CHUNK = 1024      # samples per image in one decoder call (the kernels' SVAE_IW_MAX_SAMPLES)
+INFER_PATH_OVERRIDES = ("train_path", "test_path", "ctf_train", "ctf_test")
+
+
+def infer_arguments(argv=None):
+    """infer.py's command line.  Everything after a bare `--` is kept aside (args.train_argv): with --generator/--inference
+    it is the training script's own flags, parsed later by that script's parser.  Refusals (exit code 2) are made here, before
+    anything touches a GPU or loads the kernel library."""
+    import argparse
+    argv = list(sys.argv[1:] if argv is None else argv)
+    train_argv = None
+    if "--" in argv:
+        cut = argv.index("--")
+        argv, train_argv = argv[:cut], argv[cut + 1:]
+    p = argparse.ArgumentParser("infer.py", description="Per-image pose, latents and K-sample importance-weighted likelihood "
+                                "of a trained spatial-VAE")
+    p.add_argument("script", choices=sorted(SCRIPTS), help="which training script made the model")
+    p.add_argument("--state", metavar="PATH.ckpt", help="training state file (--checkpoint_interval): model, arguments, dataset")
+    p.add_argument("--generator", metavar="G.sav", help="whole-module generator file; with --inference and, after `--`, the "
+                   "training script's own flags")
+    p.add_argument("--inference", metavar="Q.sav")
+    p.add_argument("--out", required=True, metavar="scores.npz")
+    p.add_argument("--split", choices=["test", "train"], default="test")
+    p.add_argument("--num_samples", type=int, default=64, metavar="K", help="samples per image (any K >= 1; default 64)")
+    p.add_argument("--chunk", type=int, default=64, metavar="C",
+                   help="samples per image decoded at once, 1..%d (default 64): memory is that of a B*C minibatch" % INFER_MAX_CHUNK)
+    p.add_argument("--minibatch_size", type=int, default=100, metavar="B")
+    p.add_argument("--seed", type=int, default=0, help="seed of the generator the N(0,1) draws come from")
+    p.add_argument("-d", "--device", type=int, default=-2)
+    for name in INFER_PATH_OVERRIDES:
+        p.add_argument("--" + name, default=None, help="instead of the path stored in the state file")
+    args = p.parse_args(argv)
+    args.train_argv = train_argv
+    if args.num_samples < 1:
+        p.error("--num_samples must be >= 1")
+    if not 1 <= args.chunk <= INFER_MAX_CHUNK:
+        p.error("--chunk must be in [1, %d]" % INFER_MAX_CHUNK)
+    if args.minibatch_size < 1:
+        p.error("--minibatch_size must be >= 1")
+    sav = args.generator is not None or args.inference is not None
+    if (args.state is None) == (not sav):
+        p.error("give either --state or --generator with --inference")
+    if sav and (args.generator is None or args.inference is None):
+        p.error("--generator and --inference go together")
+    if sav and train_argv is None:
+        p.error("--generator/--inference need the training script's flags after `--`")
+    if not sav and train_argv:
+        p.error("--state carries the training arguments: nothing may follow `--`")
+    for path in (args.state, args.generator, args.inference):
+        if path is not None and not os.path.isfile(path):
+            p.error("no such file: %s" % path)
+    return args
+
+
+def _refuse(message):
+    print("infer.py: " + message, file=sys.stderr)
+    raise SystemExit(2)
+
+
+def stored_namespace(ck, defaults, script):
+    """The training run's argument namespace from a state file: the stored arguments over RESUME_ARG_DEFAULTS over the
+    script's own defaults.  A file another script wrote names arguments this script's parser does not have (and lacks some it
+    has): refused, exit code 2."""
+    import argparse
+    stored = dict(ck["args"])
+    unknown = sorted(set(stored) - set(defaults))
+    missing = sorted(set(defaults) - set(stored) - set(RESUME_ARG_DEFAULTS))
+    if unknown or missing:
+        _refuse("the state file was not written by train_{}.py: it has the arguments {} which that script lacks, and lacks {}"
+                .format(script, unknown, missing))
+    return argparse.Namespace(**dict(defaults, **dict(RESUME_ARG_DEFAULTS, **stored)))
+
+
+def write_npz(path, arrays):
+    """One .npz of plain arrays, written under a temporary name beside `path` and renamed over it: an interrupted write leaves
+    no file under the final name."""
+    tmp = "{}.tmp{}".format(path, os.getpid())
+    try:
+        with open(tmp, "wb") as f:
+            np.savez(f, **arrays)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return path
+
+
+def read_npz(path):
+    with np.load(path, allow_pickle=False) as f:
+        return {k: f[k] for k in f.files}
+
+
+def score_arrays(per_image, q_mu, q_std, rotate, translate):
+    """The named arrays of infer.py's output from the rows of elbo.score_minibatch (host arrays): theta_* iff the model rotates,
+    dx_* iff it translates."""
+    inf_dim = q_mu.shape[1]
+    off = 1 if rotate else 0
+    c0 = off + (2 if translate else 0)
+    iw, best = per_image[:, 6:6 + inf_dim], per_image[:, 6 + inf_dim:6 + 2 * inf_dim]
+    out = {"bound": per_image[:, 0], "loglik": per_image[:, 1], "kl": per_image[:, 2], "ess": per_image[:, 3]}
+    if rotate:
+        out.update(theta_q=q_mu[:, 0], theta_q_std=q_std[:, 0], theta_iw=iw[:, 0], theta_R=per_image[:, 5], theta_best=best[:, 0])
+    if translate:
+        out.update(dx_q=q_mu[:, off:c0], dx_q_std=q_std[:, off:c0], dx_iw=iw[:, off:c0], dx_best=best[:, off:c0])
+    out.update(z_q=q_mu[:, c0:], z_q_std=q_std[:, c0:], z_iw=iw[:, c0:], z_best=best[:, c0:])
+    out["index"] = np.arange(per_image.shape[0], dtype=np.int64)
+    return {k: np.ascontiguousarray(v) for k, v in out.items()}
+
+
+def infer_main(args, parser_fn, build, positional=()):
+    """infer.py after its own parsing.  parser_fn(argv) is the training script's parser, build(args, device) its dataset and
+    network builder, `positional` stand-ins for its positional arguments when only its defaults are wanted."""
+    import json
+    script = args.script
+    rule = SCRIPTS[script]
+    ck = None
+    overridden = [n for n in INFER_PATH_OVERRIDES if getattr(args, n) is not None]
+    if args.state is not None:
+        try:
+            ck = read_checkpoint(args.state)
+        except CheckpointError as e:
+            _refuse(str(e).replace("--resume: ", ""))
+        targs = stored_namespace(ck, vars(parser_fn(list(positional))), script)
+        for n in overridden:
+            if not hasattr(targs, n):
+                _refuse("train_{}.py has no --{} to override".format(script, n))
+            setattr(targs, n, getattr(args, n))
+        completed = int(ck["completed"])
+    else:
+        targs = parser_fn(args.train_argv)
+        completed = targs.num_epochs
+    device = pick_device(args.device)
+    if targs.seed is not None:                      # build() must make the split the run trained on (galaxy shuffles in it)
+        torch.manual_seed(targs.seed)
+        np.random.seed(targs.seed % (2 ** 32))
+    if targs.gemm:
+        from . import _lib
+        _lib.set_gemm_mode(targs.gemm)
+    cfg = build(targs, device)
+    if ck is not None:
+        if not overridden:
+            try:
+                check_resume_fingerprint(ck, dataset_fingerprint(cfg["y_train"], cfg["y_test"]))
+            except CheckpointError as e:
+                _refuse(str(e).replace("--resume: ", ""))
+        try:
+            cfg["p_net"].load_state_dict(ck["train_step"]["p_net"])
+            cfg["q_net"].load_state_dict(ck["train_step"]["q_net"])
+        except (RuntimeError, KeyError) as e:
+            _refuse("the state file's networks do not fit what train_{}.py builds from its arguments: {}".format(
+                script, str(e).splitlines()[0]))
+        p_net, q_net = cfg["p_net"], cfg["q_net"]
+    else:
+        p_net = torch.load(args.generator, map_location="cpu", weights_only=False)
+        q_net = torch.load(args.inference, map_location="cpu", weights_only=False)
+    p_net, q_net = p_net.to(device).eval(), q_net.to(device).eval()
+    rotate, translate = cfg["rotate"], cfg["translate"]
+    z_scale = (0 if completed < getattr(targs, "z_delay", 0) else 1) if rule.z_schedule else 1
+    data = cfg["y_" + args.split].to(device)
+    ctf = cfg.get("ctf_" + args.split)
+    ctf = ctf.to(device) if ctf is not None else None
+    mask = cfg.get("mask")
+    mask = mask.to(device) if mask is not None else None
+    x = coord_grid(cfg["n"], cfg["m"]).to(device)
+    inf_dim = q_net.latent_dim
+    K, bs = args.num_samples, args.minibatch_size
+    gen = torch.Generator()
+    gen.manual_seed(args.seed)
+    rows = []
+    for lo in range(0, data.size(0), bs):           # dataset order, nothing read back inside the loop
+        y = data[lo:lo + bs]
+        noise = torch.empty(y.size(0) * K, inf_dim).normal_(generator=gen).to(device, non_blocking=True)
+        out = E.score_minibatch(script, x, y, p_net, q_net, num_samples=K, chunk=min(args.chunk, K), rotate=rotate,
+                                translate=translate, dx_scale=targs.dx_scale, theta_prior=targs.theta_prior, z_scale=z_scale,
+                                mask=mask, ctf=None if ctf is None else ctf[lo:lo + bs], noise=noise)
+        rows.append(torch.cat([out["per_image"], out["q_mu"], out["q_std"]], 1))
+    host = torch.cat(rows).cpu().numpy()            # the one transfer
+    width = 6 + 2 * inf_dim
+    arrays = score_arrays(host[:, :width], host[:, width:width + inf_dim], host[:, width + inf_dim:], rotate, translate)
+    means = [float(np.mean(arrays[k], dtype=np.float64)) for k in ("bound", "loglik", "kl")]
+    arrays["meta"] = np.array(json.dumps({
+        "script": script, "state": args.state, "generator": args.generator, "inference": args.inference, "num_samples": K,
+        "chunk": args.chunk, "seed": args.seed, "split": args.split, "images": int(host.shape[0]),
+        "mean_bound": means[0], "mean_loglik": means[1], "mean_kl": means[2]}))
+    write_npz(args.out, arrays)
+    print("images {}\tbound {!r}\tlog p(x|z) {!r}\tKL {!r}\tmedian ESS {:.3f}".format(
+        host.shape[0], means[0], means[1], means[2], float(np.median(arrays["ess"]))))
+    return 0

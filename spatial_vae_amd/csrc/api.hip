@@ -13,10 +13,12 @@
 #include <vector>
 
 #include "common.h"
+#include "../../include/svae_stream.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
 #include "elementwise.h"
+#include "iw_stream.h"
 #include "encoder.h"
 #include "split.h"
 
@@ -1443,6 +1445,98 @@ int svae_iw_head_backward(const float* g_bound, const float* g_logp, const float
     hipLaunchKernelGGL(iw_head_bwd_kernel, dim3(blocks_for((long)B * K)), dim3(256), 0, st, g_bound, g_logp, g_kl, weights, B,
                        K, dloglik, dlog_ratio);
     return launch_status("svae_iw_head_backward");
+}
+
+// ---- streaming K-sample scorer (include/svae_stream.h) ----
+namespace {
+// What each state address was last reset for, and the chunks merged since: lets update / finish refuse a mismatch without
+// reading the device.  One entry per address, replaced by the next reset of that address.
+struct StreamInfo {
+    int32_t B, inf;
+    int64_t chunks;
+};
+std::mutex g_stream_mu;
+std::unordered_map<const void*, StreamInfo> g_streams;
+
+int stream_lookup(const char* who, const void* state, int32_t B, int32_t inf, StreamInfo* out) {
+    if (!state) return fail(SVAE_E_INVALID, "%s: null state", who);
+    std::lock_guard<std::mutex> lk(g_stream_mu);
+    const auto it = g_streams.find(state);
+    if (it == g_streams.end()) return fail(SVAE_E_INVALID, "%s: the state was never reset (svae_iw_stream_reset)", who);
+    if (it->second.B != B || it->second.inf != inf)
+        return fail(SVAE_E_INVALID, "%s: descriptor has B = %d, inf_dim = %d; the state was reset for B = %d, inf_dim = %d", who, B,
+                    inf, it->second.B, it->second.inf);
+    *out = it->second;
+    return SVAE_OK;
+}
+}  // namespace
+
+size_t svae_iw_stream_state_bytes(int32_t B, int32_t inf_dim) {
+    if (B < 1 || inf_dim < 1) return 0;
+    return (size_t)B * (size_t)iws_stride(inf_dim) * sizeof(double);
+}
+
+int svae_iw_stream_reset(void* state, int32_t B, int32_t inf_dim, svae_stream_t stream) {
+    if (!state || B < 1 || inf_dim < 1) return fail(SVAE_E_INVALID, "svae_iw_stream_reset: bad arguments (B = %d, inf_dim = %d)", B, inf_dim);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    {
+        Scope prof(K_LATENT, st);
+        hipLaunchKernelGGL(iw_stream_reset_kernel, dim3(blocks_for((long)B * iws_stride(inf_dim))), dim3(256), 0, st,
+                           static_cast<double*>(state), B, inf_dim);
+        rc = launch_status("svae_iw_stream_reset");
+    }
+    if (rc == SVAE_OK) {
+        std::lock_guard<std::mutex> lk(g_stream_mu);
+        g_streams[state] = StreamInfo{B, inf_dim, 0};
+    }
+    return rc;
+}
+
+int svae_iw_stream_update(void* state, const svae_latent_desc* d, int32_t K, const float* loglik, const float* log_ratio,
+                          const float* theta, const float* dx, const float* zc, svae_stream_t stream) {
+    LatentGeo g;
+    StreamInfo info;
+    int rc;
+    if ((rc = latent_geo(d, &g))) return rc;
+    if ((rc = iw_samples("svae_iw_stream_update", g.B, K))) return rc;
+    const int zd = g.inf - g.rotate - 2 * g.translate;
+    if (!loglik || !log_ratio || (g.rotate && !theta) || (g.translate && !dx) || (zd > 0 && !zc))
+        return fail(SVAE_E_INVALID, "svae_iw_stream_update: null pointer");
+    if ((rc = stream_lookup("svae_iw_stream_update", state, g.B, g.inf, &info))) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    {
+        Scope prof(K_LATENT, st);
+        int width = 1;                                               // iw_group_width(K): lanes per image
+        while (width < K && width < 64) width <<= 1;
+        const int per_block = 256 / width;
+        hipLaunchKernelGGL(iw_stream_update_kernel, dim3((unsigned)((g.B + per_block - 1) / per_block)), dim3(256), 0, st,
+                           static_cast<double*>(state), loglik, log_ratio, theta, dx, zc, K, g);
+        rc = launch_status("svae_iw_stream_update");
+    }
+    if (rc == SVAE_OK) {
+        std::lock_guard<std::mutex> lk(g_stream_mu);
+        const auto it = g_streams.find(state);
+        if (it != g_streams.end()) it->second.chunks += 1;
+    }
+    return rc;
+}
+
+int svae_iw_stream_finish(const void* state, const svae_latent_desc* d, float* per_image, float* out3, svae_stream_t stream) {
+    LatentGeo g;
+    StreamInfo info;
+    int rc;
+    if ((rc = latent_geo(d, &g))) return rc;
+    if (!per_image) return fail(SVAE_E_INVALID, "svae_iw_stream_finish: null pointer");
+    if ((rc = stream_lookup("svae_iw_stream_finish", state, g.B, g.inf, &info))) return rc;
+    if (info.chunks < 1) return fail(SVAE_E_INVALID, "svae_iw_stream_finish: no chunk has been merged since the reset");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_LATENT, st);
+    hipLaunchKernelGGL(iw_stream_finish_kernel, dim3(blocks_for(g.B)), dim3(256), 0, st, static_cast<const double*>(state),
+                       per_image, g.B, g.inf, g.rotate);
+    if (out3)
+        hipLaunchKernelGGL(iw_stream_means_kernel, dim3(1), dim3(256), 0, st, static_cast<const double*>(state), out3, g.B, g.inf);
+    return launch_status("svae_iw_stream_finish");
 }
 
 int svae_colsum(const float* x, int32_t rows, int32_t cols, float* out, svae_stream_t stream) {

@@ -94,6 +94,24 @@ def _augment(script, y, rotate, offset):
     return ops.rotate_augment(y, offset, side, side, quantize_u8=(script == "galaxy")), offset
 
 
+def _decode_score(script, x, y, p_net, B, theta, dx, zc, mask, ctf):
+    """Pose -> decoder -> per-row log-likelihood for B rows (images, or samples of images): (y_hat, logits, loglik)."""
+    loglik = None
+    if hasattr(p_net, "forward_posed"):
+        if script == "particles" or getattr(p_net, "softplus", False):
+            y_hat, logits = p_net.forward_posed(x, B, theta=theta, dx=dx, z=zc, return_logits=True)
+        else:   # Bernoulli likelihood: scored inside the decoder call (no second pass over y_hat, no scaling pass backward)
+            y_hat, logits, loglik = p_net.forward_posed(x, B, theta=theta, dx=dx, z=zc, bce_target=y)
+    else:                                           # --vanilla baseline: ignores coordinates
+        y_hat, logits = p_net(x, zc), None
+
+    if script == "particles":
+        loglik = ops.gaussian_loglik(y_hat.reshape(B, -1), y.view(B, -1), mask=mask, ctf=ctf)
+    elif loglik is None:
+        loglik = ops.bce_loglik(y_hat.reshape(B, -1), y.reshape(B, -1))
+    return y_hat, logits, loglik
+
+
 def _core(script, x, y, p_net, q_net, rotate, translate, dx_scale, theta_prior, z_scale, mask, ctf, noise, use_cuda,
           augment_rotation=False, offset=None, num_samples=1):
     B = y.size(0)
@@ -131,19 +149,7 @@ def _core(script, x, y, p_net, q_net, rotate, translate, dx_scale, theta_prior, 
         turn = torch.from_numpy(offset).float().to(theta.device)
         theta = theta + (turn.repeat_interleave(K) if K > 1 else turn)
 
-    loglik = None
-    if hasattr(p_net, "forward_posed"):
-        if script == "particles" or getattr(p_net, "softplus", False):
-            y_hat, logits = p_net.forward_posed(x, B, theta=theta, dx=dx, z=zc, return_logits=True)
-        else:   # Bernoulli likelihood: scored inside the decoder call (no second pass over y_hat, no scaling pass backward)
-            y_hat, logits, loglik = p_net.forward_posed(x, B, theta=theta, dx=dx, z=zc, bce_target=y)
-    else:                                           # --vanilla baseline: ignores coordinates
-        y_hat, logits = p_net(x, zc), None
-
-    if script == "particles":
-        loglik = ops.gaussian_loglik(y_hat.reshape(B, -1), y.view(B, -1), mask=mask, ctf=ctf)
-    elif loglik is None:
-        loglik = ops.bce_loglik(y_hat.reshape(B, -1), y.reshape(B, -1))
+    y_hat, logits, loglik = _decode_score(script, x, y, p_net, B, theta, dx, zc, mask, ctf)
     if K > 1:
         elbo, log_p_x_g_z, kl_div = ops.iw_head(loglik, kl_b, K)    # log-mean-exp over each image's samples, then the batch means
     else:
@@ -176,6 +182,61 @@ def eval_minibatch_particles(x, y, mask, ctf, p_net, q_net, rotate=True, transla
                                            z_scale, mask, ctf, noise, use_cuda, augment_rotation, offset, num_samples)
     out = (elbo, log_p, kl)
     return out + (logits,) if return_logits else out
+
+
+# ---------------------------------------------------------------- per-image scoring (infer.py)
+@torch.no_grad()
+def score_minibatch(script, x, y, p_net, q_net, *, num_samples, chunk, rotate, translate, dx_scale, theta_prior, z_scale=1,
+                    mask=None, ctf=None, noise=None, return_best=False):
+    """Per-image K-sample scores of one minibatch with K unbounded: the encoder runs ONCE, then each chunk of at most `chunk`
+    samples per image goes through ops.latent_head_iw on the same q_out, the unchanged decoder and log-likelihood calls on
+    B * chunk rows, and ops.IWStream.update; peak memory is that of a B * chunk minibatch.  No counterpart in the reference.
+    noise: (B * num_samples, inf_dim), row b * num_samples + k = sample k of image b; chunk c of image b takes its rows
+    [c0, c1).  Returns {"per_image": (B, 6 + 2 * inf_dim) as svae_iw_stream_finish lays it out, "out3": {bound, log p(x|z),
+    Monte-Carlo KL} means, "q_mu", "q_std": the encoder's posterior per coordinate, translation and content in the decoder's
+    units (times dx_scale / z_scale)}, and with return_best "y_best": the posed reconstruction at each image's best sample."""
+    K, C = int(num_samples), int(chunk)
+    if K < 1:
+        raise RuntimeError("num_samples must be >= 1, got %d" % K)
+    if not 1 <= C <= ops._lib.IW_MAX_SAMPLES:
+        raise RuntimeError("chunk must be in [1, %d], got %d" % (ops._lib.IW_MAX_SAMPLES, C))
+    B = y.size(0)
+    q_out = _encode(q_net, y.view(B, -1))
+    inf_dim = q_out.size(1) // 2
+    if noise is not None:
+        if tuple(noise.shape) != (B * K, inf_dim):
+            raise RuntimeError("noise must be (%d, %d) for %d samples of %d images, got %s"
+                               % (B * K, inf_dim, K, B, tuple(noise.shape)))
+        noise = noise.view(B, K, inf_dim)
+    stream = ops.IWStream(B, inf_dim, q_out.device)
+    rep = {}                                        # the observed images (and filters) repeated per sample, by chunk size
+    for c0 in range(0, K, C):
+        kc = min(C, K - c0)
+        if noise is not None:
+            r = noise[:, c0:c0 + kc].reshape(B * kc, inf_dim)
+        else:
+            r = torch.empty(B * kc, inf_dim, device=q_out.device, dtype=torch.float32).normal_()
+        theta, dx, zc, log_ratio = ops.latent_head_iw(q_out, r, kc, rotate, translate, script == "mnist", dx_scale, z_scale,
+                                                      theta_prior)
+        if kc not in rep:
+            rep = {kc: (y.repeat_interleave(kc, 0), None if ctf is None else ctf.repeat_interleave(kc, 0))}
+        y_k, ctf_k = rep[kc]
+        _, _, loglik = _decode_score(script, x, y_k, p_net, B * kc, theta, dx, zc, mask, ctf_k)
+        stream.update(rotate, translate, script == "mnist", dx_scale, z_scale, theta_prior, kc, loglik, log_ratio, theta, dx, zc)
+    per_image, out3 = stream.finish()
+    off = 1 if rotate else 0
+    c0 = off + (2 if translate else 0)
+    unit = torch.ones(inf_dim, device=q_out.device)
+    unit[off:c0] = float(dx_scale)
+    unit[c0:] = float(z_scale)
+    out = {"per_image": per_image, "out3": out3, "q_mu": q_out[:, :inf_dim] * unit, "q_std": torch.exp(q_out[:, inf_dim:]) * unit}
+    if return_best:
+        best = per_image[:, 6 + inf_dim:]
+        theta = best[:, 0].contiguous() if rotate else None
+        dx = best[:, off:c0].contiguous() if translate else None
+        zc = best[:, c0:].contiguous()
+        out["y_best"] = _decode_score(script, x, y, p_net, B, theta, dx, zc, mask, ctf)[0]
+    return out
 
 
 # ---------------------------------------------------------------- forward-only paths (image dumps of the training scripts)

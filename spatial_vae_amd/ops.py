@@ -50,7 +50,7 @@ def _p(t):
 
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
-                 for name, (_, argtypes) in _lib.SIGNATURES.items()}
+                 for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -394,6 +394,59 @@ def iw_head(loglik, log_ratio, K):
     """(bound, log_p_x_g_z, kl_div) of a minibatch from the per-sample log-likelihoods and log p(z) - log q(z|x), each (B*K):
     three views of one vector, like elbo_head.  For K >= 2 the bound is not log_p - kl."""
     return _IWHead.apply(loglik, log_ratio, K)
+
+
+class IWStream:
+    """The streaming K-sample scorer (include/svae_stream.h) for B images of inf_dim latents: update() merges one chunk of
+    at most IW_MAX_SAMPLES samples per image, finish() gives (per_image (B, 6 + 2*inf_dim), out3) for everything merged so
+    far.  Any number of chunks; the record it keeps on the device is a few doubles per image.  Forward only."""
+
+    def __init__(self, B, inf_dim, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("spatial_vae_amd: IWStream must live on a HIP device (got %s); the MI355X path has no CPU "
+                               "fallback" % device)
+        self.B, self.inf_dim, self.device = int(B), int(inf_dim), device
+        nbytes = _lib.lib().svae_iw_stream_state_bytes(self.B, self.inf_dim)
+        if nbytes == 0:
+            raise RuntimeError("IWStream: bad B = %d or inf_dim = %d" % (self.B, self.inf_dim))
+        self.state = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+        self.reset()
+
+    def reset(self):
+        _call("svae_iw_stream_reset", self.device, self.state, self.B, self.inf_dim)
+        self._pose = None
+
+    def update(self, rotate, translate, mu_penalty, dx_scale, z_scale, theta_prior, K, loglik, log_ratio, theta, dx, zc):
+        """One chunk: loglik, log_ratio (B*K) and the theta / dx / zc that ops.latent_head_iw gave for it (the descriptor
+        arguments are latent_head_iw's); row b*K + k is sample k of image b."""
+        K = _check_samples(K)
+        for name, t in (("loglik", loglik), ("log_ratio", log_ratio), ("theta", theta), ("dx", dx), ("zc", zc)):
+            if t is not None:
+                _require_hip(t, name)
+        loglik, log_ratio, theta, dx, zc = (_f32(t) for t in (loglik, log_ratio, theta, dx, zc))
+        zd = self.inf_dim - (1 if rotate else 0) - (2 if translate else 0)
+        rows = self.B * K
+        theta, dx, zc = theta if rotate else None, dx if translate else None, zc if zd > 0 else None
+        for name, t, n in (("loglik", loglik, rows), ("log_ratio", log_ratio, rows), ("theta", theta, rows if rotate else None),
+                           ("dx", dx, 2 * rows if translate else None), ("zc", zc, zd * rows if zd > 0 else None)):
+            if (None if t is None else t.numel()) != n:
+                raise RuntimeError("IWStream.update: %s has %s elements, %s expected for %d samples of %d images"
+                                   % (name, None if t is None else t.numel(), n, K, self.B))
+        d = _lib.LatentDesc(self.B, self.inf_dim, int(bool(rotate)), int(bool(translate)), int(bool(mu_penalty)),
+                            float(dx_scale), float(z_scale), float(theta_prior))
+        _call("svae_iw_stream_update", self.device, self.state, ctypes.byref(d), K, loglik, log_ratio, theta, dx, zc)
+        self._pose = (int(bool(rotate)), int(bool(translate)))
+
+    def finish(self):
+        """(per_image, out3) of everything merged since the last reset; may be called again after further updates."""
+        if getattr(self, "_pose", None) is None:
+            raise RuntimeError("IWStream.finish: no chunk has been merged")
+        d = _lib.LatentDesc(self.B, self.inf_dim, self._pose[0], self._pose[1], 0, 1.0, 1.0, 1.0)
+        per_image = torch.empty(self.B, _lib.iw_stream_cols(self.inf_dim), dtype=torch.float32, device=self.device)
+        out3 = torch.empty(3, dtype=torch.float32, device=self.device)
+        _call("svae_iw_stream_finish", self.device, self.state, ctypes.byref(d), per_image, out3)
+        return per_image, out3
 
 
 ENC_ACT = {None: _lib.LINEAR_ACT_NONE, **_lib.ACT}

@@ -1,0 +1,158 @@
+"""CPU-only: infer.py's command line, its .npz writer, the float64 reference of the streaming scorer held to properties of
+the definitions it restates, and the binding of include/svae_stream.h held to that header."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from iw_stream_ref import coords, iw_stream_ref, wrap
+from test_binding_cpu import _allowed, parse_header
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _cli():
+    from spatial_vae_amd import cli
+    return cli
+
+
+def test_parser_defaults_and_the_split(tmp_path):
+    state = tmp_path / "a.ckpt"
+    state.write_bytes(b"x")
+    a = _cli().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz"])
+    assert (a.script, a.split, a.num_samples, a.chunk, a.minibatch_size, a.seed, a.device) == ("mnist", "test", 64, 64, 100, 0, -2)
+    assert a.train_argv is None and a.generator is None and a.train_path is None and a.ctf_test is None
+    g, q = tmp_path / "g.sav", tmp_path / "q.sav"
+    g.write_bytes(b"x")
+    q.write_bytes(b"x")
+    a = _cli().infer_arguments(["particles", "--generator", str(g), "--inference", str(q), "--out", "s.npz", "--num_samples", "5000",
+                                "--chunk", "50", "--", "tr.mrcs", "te.mrcs", "--z-dim", "4", "--out", "not-ours"])
+    assert a.train_argv == ["tr.mrcs", "te.mrcs", "--z-dim", "4", "--out", "not-ours"] and a.out == "s.npz"
+    assert (a.num_samples, a.chunk, a.state) == (5000, 50, None)
+
+
+@pytest.mark.parametrize("argv,message", [
+    (["mnist", "--state", "{state}", "--out", "s.npz", "--num_samples", "0"], "num_samples"),
+    (["mnist", "--state", "{state}", "--out", "s.npz", "--chunk", "0"], "chunk"),
+    (["mnist", "--state", "{state}", "--out", "s.npz", "--chunk", "1025"], "chunk"),
+    (["mnist", "--state", "{missing}", "--out", "s.npz"], "no such file"),
+    (["mnist", "--out", "s.npz"], "--state"),
+    (["mnist", "--state", "{state}", "--out", "s.npz", "--", "--z_dim", "3"], "nothing may follow"),
+    (["mnist", "--generator", "{state}", "--out", "s.npz", "--"], "go together"),
+    (["mnist", "--generator", "{state}", "--inference", "{state}", "--out", "s.npz"], "after `--`"),
+])
+def test_refusals_exit_with_code_2_before_the_library_is_loaded(tmp_path, argv, message):
+    """Through the real command line in a fresh process: exit code 2, the reason on stderr, no output file, and the process
+    never loaded the kernel library (a marker printed by an exit hook shows _lib's handle was still unset)."""
+    state = tmp_path / "a.ckpt"
+    state.write_bytes(b"x")
+    argv = [a.format(state=state, missing=tmp_path / "nope.ckpt") for a in argv]
+    code = ("import atexit, sys; sys.path.insert(0, %r); sys.argv = ['infer.py'] + %r\n"
+            "from spatial_vae_amd import _lib\n"
+            "atexit.register(lambda: print('LIB', _lib._lib is None, file=sys.stderr))\n"
+            "import infer; sys.exit(infer.main())" % (ROOT, argv))
+    out = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2, out.stderr[-2000:]
+    assert message in out.stderr and "LIB True" in out.stderr
+    assert not os.path.exists(tmp_path / "s.npz")
+
+
+def test_state_file_of_another_script_is_refused(tmp_path):
+    """A state file whose stored arguments are not the named script's: exit code 2 from stored_namespace, which runs before a
+    device is picked."""
+    import train_galaxy
+    import train_mnist
+    cli = _cli()
+    stored = cli.plain_args(train_galaxy.galaxy_arguments(["a.npy", "b.npy", "--synthetic", "8"]))
+    with pytest.raises(SystemExit) as e:
+        cli.stored_namespace({"args": stored}, vars(train_mnist.mnist_arguments([])), "mnist")
+    assert e.value.code == 2
+    mine = cli.plain_args(train_mnist.mnist_arguments(["--z_dim", "5"]))
+    for k in cli.RESUME_ARG_DEFAULTS:          # a file from before these options existed
+        mine.pop(k)
+    ns = cli.stored_namespace({"args": mine}, vars(train_mnist.mnist_arguments([])), "mnist")
+    assert ns.z_dim == 5 and ns.num_samples == 1 and ns.clip_grad_norm is None
+
+
+def test_npz_round_trip_and_interrupted_write(tmp_path, monkeypatch):
+    cli = _cli()
+    rs = np.random.RandomState(0)
+    per_image = rs.normal(size=(7, 6 + 2 * 6)).astype(np.float32)
+    q_mu, q_std = rs.normal(size=(7, 6)).astype(np.float32), rs.uniform(size=(7, 6)).astype(np.float32)
+    arrays = cli.score_arrays(per_image, q_mu, q_std, True, True)
+    arrays["meta"] = np.array(json.dumps({"k": 1}))
+    path = str(tmp_path / "s.npz")
+    cli.write_npz(path, arrays)
+    back = cli.read_npz(path)                                   # allow_pickle=False: plain arrays only
+    assert sorted(back) == sorted(arrays) and all(np.array_equal(back[k], arrays[k]) for k in arrays)
+    assert json.loads(str(back["meta"])) == {"k": 1} and os.listdir(tmp_path) == ["s.npz"]
+    assert np.array_equal(back["theta_iw"], per_image[:, 6]) and np.array_equal(back["dx_best"], per_image[:, 13:15])
+    assert np.array_equal(back["z_q"], q_mu[:, 3:]) and np.array_equal(back["theta_R"], per_image[:, 5])
+    no_rot = cli.score_arrays(per_image[:, :6 + 2 * 5], q_mu[:, :5], q_std[:, :5], False, True)
+    assert not [k for k in no_rot if k.startswith("theta_")] and no_rot["dx_iw"].shape == (7, 2) and no_rot["z_iw"].shape == (7, 3)
+    no_dx = cli.score_arrays(per_image[:, :6 + 2 * 4], q_mu[:, :4], q_std[:, :4], True, False)
+    assert not [k for k in no_dx if k.startswith("dx_")] and no_dx["z_best"].shape == (7, 3)
+
+    def broken(f, **kw):
+        f.write(b"half a file")
+        raise KeyboardInterrupt
+    monkeypatch.setattr(np, "savez", broken)
+    other = str(tmp_path / "t.npz")
+    with pytest.raises(KeyboardInterrupt):
+        cli.write_npz(other, arrays)
+    with pytest.raises(KeyboardInterrupt):
+        cli.write_npz(path, arrays)                             # nor is an earlier file damaged
+    assert os.listdir(tmp_path) == ["s.npz"] and sorted(cli.read_npz(path)) == sorted(arrays)
+
+
+def test_reference_holds_to_properties_of_the_definitions():
+    """Independent of how the reference is written: the bound of K equal values is that value and their sample size is K; the
+    circular mean of {pi - eps, -pi + eps} under equal weights is +-pi with R = cos(eps); a = -inf samples weigh nothing; the
+    best sample is the first at the max."""
+    K, eps = 7, 0.05
+    v = np.zeros((1, K, 2))
+    row, out3, w = iw_stream_ref(np.full((1, K), -3.25), np.full((1, K), 0.75), v, False)
+    assert abs(row[0, 0] - (-2.5)) < 1e-14 and abs(row[0, 3] - K) < 1e-12 and np.allclose(w, 1.0 / K)
+    assert row[0, 5] == 1 and abs(out3[0] + 2.5) < 1e-14 and out3[1] == -3.25 and out3[2] == -0.75
+    v = np.array([[[np.pi - eps, 1.0], [-np.pi + eps, 3.0]]])
+    row, _, _ = iw_stream_ref(np.zeros((1, 2)), np.zeros((1, 2)), v, True)
+    assert abs(abs(row[0, 6]) - np.pi) < 1e-12 and abs(row[0, 5] - np.cos(eps)) < 1e-12 and abs(row[0, 7] - 2.0) < 1e-14
+    assert abs(wrap(row[0, 6] - np.pi)) < 1e-12
+    ll = np.array([[0.0, 0.0, 0.0, 0.0]])
+    lr = np.array([[-np.inf, 1.0, 1.0, -np.inf]])
+    v = np.arange(4.0).reshape(1, 4, 1)
+    row, _, w = iw_stream_ref(ll, lr, v, False)
+    assert (w[0] == [0, 0.5, 0.5, 0]).all() and row[0, 3] == 2 and row[0, 6] == 1.5 and row[0, 7] == 1.0 and row[0, 4] == 1.0
+    assert abs(row[0, 0] - (1.0 + np.log(2.0 / 4.0))) < 1e-14
+    row, out3, _ = iw_stream_ref(ll, np.full((1, 4), -np.inf), v, True)
+    assert row[0, 0] == -np.inf and row[0, 3] == 0 and row[0, 5] == 0 and row[0, 6] == 0 and row[0, 7] == 0.0
+    assert coords(np.zeros(6), np.zeros((6, 2)), np.zeros((6, 3)), 2, 3).shape == (2, 3, 6)
+
+
+def test_stream_binding_matches_its_header():
+    """include/svae_stream.h against _lib.STREAM_SIGNATURES, both ways and type by type, with the parser and the type rules
+    tests/test_binding_cpu.py uses for svae.h; the header adds no struct and no integer constant, and its one macro is
+    _lib.iw_stream_cols."""
+    from spatial_vae_amd import _lib
+    with open(os.path.join(ROOT, "include", "svae_stream.h")) as f:
+        text = f.read()
+    H = parse_header(text.replace('#include "svae.h"', ""))
+    assert H["structs"] == {} and H["constants"] == {} and len(H["functions"]) == 4
+    assert set(H["functions"]) == set(_lib.STREAM_SIGNATURES) == set(_lib.declared_in_header(os.path.join(ROOT, "include", "svae_stream.h")))
+    assert not set(_lib.STREAM_SIGNATURES) & set(_lib.SIGNATURES)
+    for name, ((rbase, rptr), args) in H["functions"].items():
+        restype, argtypes = _lib.STREAM_SIGNATURES[name]
+        assert restype in _allowed(rbase, rptr, _lib), name
+        assert len(args) == len(argtypes), name
+        for (base, pointer, arg), have in zip(args, argtypes):
+            assert have in _allowed(base, pointer, _lib, arg == "state"), (name, arg)
+    assert "#define SVAE_IW_STREAM_COLS(inf_dim) (6 + 2 * (inf_dim))" in text
+    assert [_lib.iw_stream_cols(i) for i in (1, 5)] == [8, 16]
+    L = _lib.lib()
+    for name, (restype, argtypes) in _lib.STREAM_SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    assert L.svae_abi_version() == 2
