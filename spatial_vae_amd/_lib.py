@@ -125,6 +125,17 @@ def iw_stream_cols(inf_dim):
     return 6 + 2 * int(inf_dim)
 
 
+# ---- include/svae_align.h: alignment into the canonical frame and class sums, a third header with a table of its own ----
+# Same rules again (tests/test_align_cpu.py holds these rows to that header's prototypes).  The header's two constants are the
+# values of ALIGN_INTERP, under SVAE_ALIGN_<NAME>: a name table like ACT, because the upper-case integers of this module are
+# svae.h's constants and nothing else.
+ALIGN_SIGNATURES = {
+    "svae_align_images": (cint, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "svae_class_sums_update": (cint, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+}
+ALIGN_INTERP = {"bilinear": 0, "bicubic": 1}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -147,7 +158,7 @@ def lib():
         raise RuntimeError("spatial_vae_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
-    for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from . import dp
 from . import elbo as E
+from . import ops
 
 
 class RunningMean(object):
@@ -716,6 +717,8 @@ def synthetic_images(kind, count, n, m, channels, seed):
 # ---- infer.py: apply a trained model to a dataset, one row per image --------------------------------------------------------
 INFER_MAX_CHUNK = 1024      # samples per image in one decoder call (the kernels' SVAE_IW_MAX_SAMPLES)
 INFER_PATH_OVERRIDES = ("train_path", "test_path", "ctf_train", "ctf_test")
+INFER_MAX_CLASSES = 4096    # classes of --labels (svae_class_sums_update's limit)
+INFER_STACK_FORMATS = (".npy", ".mrcs")
 
 
 def infer_arguments(argv=None):
@@ -745,6 +748,19 @@ def infer_arguments(argv=None):
     p.add_argument("-d", "--device", type=int, default=-2)
     for name in INFER_PATH_OVERRIDES:
         p.add_argument("--" + name, default=None, help="instead of the path stored in the state file")
+    p.add_argument("--aligned", metavar="PATH", help="also write every image brought into the model's canonical frame (its "
+                   "pose removed), in dataset order: .npy = (images, rows, cols, C) float32, .mrcs = an MRC stack (one channel "
+                   "only).  The observed images resampled, nothing else: not CTF-corrected, not masked")
+    p.add_argument("--recon", metavar="PATH", help="also write every image's pose-free reconstruction (the decoder on the "
+                   "un-posed grid at the image's content latents), same formats")
+    p.add_argument("--class_averages", metavar="PATH.npz", help="also write the sums, counts and averages of the aligned images "
+                   "over the pixels each image covers: per class of --labels, else one class of all images")
+    p.add_argument("--labels", metavar="PATH.npy", help="integer class per image of the split, -1 = in no class (with "
+                   "--class_averages; at most %d classes)" % INFER_MAX_CLASSES)
+    p.add_argument("--pose", choices=list(E.POSES), default=None, help="which estimate aligns, and whose content latents --recon "
+                   "decodes: the importance-weighted mean (iw, the default), the best sample, or q's mean")
+    p.add_argument("--interp", choices=["bicubic", "bilinear"], default=None, help="resampling of --aligned / --class_averages "
+                   "(default bicubic: Catmull-Rom)")
     args = p.parse_args(argv)
     args.train_argv = train_argv
     if args.num_samples < 1:
@@ -765,7 +781,47 @@ def infer_arguments(argv=None):
     for path in (args.state, args.generator, args.inference):
         if path is not None and not os.path.isfile(path):
             p.error("no such file: %s" % path)
+    for name in ("aligned", "recon"):
+        path = getattr(args, name)
+        if path is not None and os.path.splitext(path)[1] not in INFER_STACK_FORMATS:
+            p.error("--%s must end in .npy or .mrcs (got %s)" % (name, path))
+    if args.class_averages is not None and os.path.splitext(args.class_averages)[1] != ".npz":
+        p.error("--class_averages must end in .npz (got %s)" % args.class_averages)
+    if args.labels is not None and args.class_averages is None:
+        p.error("--labels needs --class_averages")
+    if args.aligned is None and args.recon is None and args.class_averages is None:
+        for name in ("pose", "interp"):
+            if getattr(args, name) is not None:
+                p.error("--%s needs one of --aligned, --recon, --class_averages" % name)
+    args.pose, args.interp = args.pose or "iw", args.interp or "bicubic"
+    args.label_array = None
+    if args.labels is not None:
+        try:
+            args.label_array = read_labels(args.labels)
+        except ValueError as e:
+            p.error(str(e))
     return args
+
+
+def read_labels(path):
+    """The int64 class labels of a --labels file; ValueError with the reason when it is no 1-D integer .npy with values >= -1
+    and at most INFER_MAX_CLASSES classes."""
+    if not os.path.isfile(path):
+        raise ValueError("no such file: %s" % path)
+    try:
+        labels = np.load(path, allow_pickle=False)
+    except Exception as e:
+        raise ValueError("--labels %s is not a .npy array: %s" % (path, e))
+    if not isinstance(labels, np.ndarray) or labels.dtype.kind not in "iu":
+        raise ValueError("--labels %s must be an integer array (got %s)" % (path, getattr(labels, "dtype", type(labels).__name__)))
+    if labels.ndim != 1:
+        raise ValueError("--labels %s must be 1-D, one entry per image (got shape %s)" % (path, labels.shape))
+    labels = labels.astype(np.int64)
+    if labels.size and labels.min() < -1:
+        raise ValueError("--labels %s has a value below -1 (%d)" % (path, labels.min()))
+    if labels.size and labels.max() + 1 > INFER_MAX_CLASSES:
+        raise ValueError("--labels %s has %d classes, at most %d are supported" % (path, labels.max() + 1, INFER_MAX_CLASSES))
+    return labels
 
 
 def _refuse(message):
@@ -787,18 +843,31 @@ def stored_namespace(ck, defaults, script):
     return argparse.Namespace(**dict(defaults, **dict(RESUME_ARG_DEFAULTS, **stored)))
 
 
-def write_npz(path, arrays):
-    """One .npz of plain arrays, written under a temporary name beside `path` and renamed over it: an interrupted write leaves
-    no file under the final name."""
+def write_atomically(path, save):
+    """save(f) writes the open binary file f; the file is written under a temporary name beside `path` and renamed over it: an
+    interrupted write leaves no file under the final name."""
     tmp = "{}.tmp{}".format(path, os.getpid())
     try:
         with open(tmp, "wb") as f:
-            np.savez(f, **arrays)
+            save(f)
         os.replace(tmp, path)
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
     return path
+
+
+def write_npz(path, arrays):
+    """One .npz of plain arrays, written under a temporary name beside `path` and renamed over it."""
+    return write_atomically(path, lambda f: np.savez(f, **arrays))
+
+
+def write_stack(path, stack):
+    """An image stack (images, rows, cols, C) float32 as .npy, or as an MRC stack (C == 1), by the path's extension."""
+    if path.endswith(".mrcs"):
+        from . import mrc
+        return write_atomically(path, lambda f: mrc.write(f, stack[..., 0]))
+    return write_atomically(path, lambda f: np.save(f, stack))
 
 
 def read_npz(path):
@@ -880,24 +949,65 @@ def infer_main(args, parser_fn, build, positional=()):
     x = coord_grid(cfg["n"], cfg["m"]).to(device)
     inf_dim = q_net.latent_dim
     K, bs = args.num_samples, args.minibatch_size
+    # the optional image outputs (--aligned, --recon, --class_averages); getattr: a caller's namespace from before they existed
+    want = {k: getattr(args, k, None) for k in ("aligned", "recon", "class_averages")}
+    images, n, m = data.size(0), cfg["n"], cfg["m"]
+    channels = data[0].numel() // (n * m) if images else 1
+    labels = getattr(args, "label_array", None)
+    if labels is not None and labels.shape[0] != images:
+        _refuse("--labels has {} entries, the {} split has {} images".format(labels.shape[0], args.split, images))
+    for k in ("aligned", "recon"):
+        if want[k] is not None and want[k].endswith(".mrcs") and channels != 1:
+            _refuse("--{} {}: an MRC stack holds one channel, these images have {}".format(k, want[k], channels))
+    stacks = {k: torch.empty(images, n * m * channels, dtype=torch.float32, pin_memory=True)      # filled by non-blocking copies
+              for k in ("aligned", "recon") if want[k] is not None}
+    sums = None
+    if want["class_averages"] is not None:
+        if labels is None:
+            labels = np.zeros(images, np.int64)     # one class holding every image
+        n_classes = max(int(labels.max()) + 1, 1) if images else 1
+        sums = ops.ClassSums(n_classes, n * m, channels, device)
+        label_d = torch.from_numpy(labels.astype(np.int32)).to(device)
     gen = torch.Generator()
     gen.manual_seed(args.seed)
     rows = []
-    for lo in range(0, data.size(0), bs):           # dataset order, nothing read back inside the loop
+    for lo in range(0, images, bs):                 # dataset order, nothing read back inside the loop
         y = data[lo:lo + bs]
         noise = torch.empty(y.size(0) * K, inf_dim).normal_(generator=gen).to(device, non_blocking=True)
         out = E.score_minibatch(script, x, y, p_net, q_net, num_samples=K, chunk=min(args.chunk, K), rotate=rotate,
                                 translate=translate, dx_scale=targs.dx_scale, theta_prior=targs.theta_prior, z_scale=z_scale,
                                 mask=mask, ctf=None if ctf is None else ctf[lo:lo + bs], noise=noise)
         rows.append(torch.cat([out["per_image"], out["q_mu"], out["q_std"]], 1))
-    host = torch.cat(rows).cpu().numpy()            # the one transfer
+        if "aligned" in stacks or sums is not None:
+            aligned, cover = E.align_minibatch(y, n, m, out["per_image"], out["q_mu"], rotate, translate, args.pose, args.interp)
+            if sums is not None:
+                sums.update(aligned, cover, label_d[lo:lo + bs])
+            if "aligned" in stacks:
+                stacks["aligned"][lo:lo + bs].copy_(aligned.view(y.size(0), -1), non_blocking=True)
+        if "recon" in stacks:
+            zc = E.content_latents(out["per_image"], out["q_mu"], rotate, translate, args.pose)
+            recon = E.reconstruct_unposed(x, p_net, y.size(0), zc, gaussian_mean=(script == "particles"))
+            stacks["recon"][lo:lo + bs].copy_(recon.reshape(y.size(0), -1), non_blocking=True)
+    host = torch.cat(rows).cpu().numpy()            # the one transfer of the scores
+    if stacks:
+        torch.cuda.synchronize(device)              # the one synchronisation: every minibatch's copy has landed
     width = 6 + 2 * inf_dim
     arrays = score_arrays(host[:, :width], host[:, width:width + inf_dim], host[:, width + inf_dim:], rotate, translate)
     means = [float(np.mean(arrays[k], dtype=np.float64)) for k in ("bound", "loglik", "kl")]
-    arrays["meta"] = np.array(json.dumps({
-        "script": script, "state": args.state, "generator": args.generator, "inference": args.inference, "num_samples": K,
-        "chunk": args.chunk, "seed": args.seed, "split": args.split, "images": int(host.shape[0]),
-        "mean_bound": means[0], "mean_loglik": means[1], "mean_kl": means[2]}))
+    meta = {"script": script, "state": args.state, "generator": args.generator, "inference": args.inference, "num_samples": K,
+            "chunk": args.chunk, "seed": args.seed, "split": args.split, "images": int(host.shape[0]),
+            "mean_bound": means[0], "mean_loglik": means[1], "mean_kl": means[2]}
+    if any(v is not None for v in want.values()):   # only then: without the options the file is what it always was
+        meta.update(pose=args.pose, interp=args.interp, labels=args.labels, **want)
+    arrays["meta"] = np.array(json.dumps(meta))
+    for k, stack in stacks.items():
+        write_stack(want[k], stack.numpy().reshape(images, n, m, channels))
+    if sums is not None:
+        total, count = (t.cpu().numpy() for t in sums.result())
+        total, count = total.reshape(sums.n_classes, n, m, channels), count.reshape(sums.n_classes, n, m)
+        average = np.divide(total, count[..., None], out=np.zeros_like(total), where=count[..., None] > 0).astype(np.float32)
+        members = np.bincount(labels[labels >= 0], minlength=sums.n_classes).astype(np.int64)
+        write_npz(want["class_averages"], {"sum": total, "count": count, "average": average, "members": members})
     write_npz(args.out, arrays)
     print("images {}\tbound {!r}\tlog p(x|z) {!r}\tKL {!r}\tmedian ESS {:.3f}".format(
         host.shape[0], means[0], means[1], means[2], float(np.median(arrays["ess"]))))

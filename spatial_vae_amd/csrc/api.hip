@@ -14,11 +14,13 @@
 
 #include "common.h"
 #include "../../include/svae_stream.h"
+#include "../../include/svae_align.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
 #include "elementwise.h"
 #include "iw_stream.h"
+#include "align.h"
 #include "encoder.h"
 #include "split.h"
 
@@ -1656,6 +1658,39 @@ int svae_rotate_bicubic(const float* y, float* y_rot, const double* matrix, cons
     else
         hipLaunchKernelGGL(rotate_bicubic_kernel<false>, dim3(blocks_for(total)), dim3(256), 0, st, y, y_rot, matrix, quarter, g);
     return launch_status("svae_rotate_bicubic");
+}
+
+// ---- alignment into the canonical frame and class sums (include/svae_align.h) ----
+int svae_align_images(const float* y, const float* theta, const float* dx, int32_t B, int32_t rows, int32_t cols, int32_t C,
+                      int32_t interp, float* aligned, uint8_t* cover, svae_stream_t stream) {
+    if (B < 1 || rows < 2 || cols < 2 || C < 1 || C > SVAE_MAX_OUT || (long)B * rows * cols * C > 0x7fffffffL)
+        return fail(SVAE_E_INVALID, "svae_align_images: bad sizes B=%d rows=%d cols=%d C=%d", B, rows, cols, C);
+    if (interp != SVAE_ALIGN_BILINEAR && interp != SVAE_ALIGN_BICUBIC)
+        return fail(SVAE_E_INVALID, "svae_align_images: unknown interpolation %d", interp);
+    const long total = (long)B * rows * cols * C;
+    if (!y || !aligned || (y < aligned + total && aligned < y + total))
+        return fail(SVAE_E_INVALID, "svae_align_images: y and aligned must be two buffers that do not overlap");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    const AlignGeo g{B, rows, cols, C};
+    if (interp == SVAE_ALIGN_BICUBIC)
+        hipLaunchKernelGGL(align_images_kernel<true>, dim3(blocks_for(total)), dim3(256), 0, st, y, theta, dx, aligned, cover, g);
+    else
+        hipLaunchKernelGGL(align_images_kernel<false>, dim3(blocks_for(total)), dim3(256), 0, st, y, theta, dx, aligned, cover, g);
+    return launch_status("svae_align_images");
+}
+
+int svae_class_sums_update(const float* aligned, const uint8_t* cover, const int32_t* label, int32_t B, int32_t N, int32_t C,
+                           int32_t n_classes, double* sum, double* count, svae_stream_t stream) {
+    if (B < 1 || N < 1 || C < 1 || C > SVAE_MAX_OUT || n_classes < 1 || n_classes > 4096 || (long)B * N * C > 0x7fffffffL ||
+        (long)n_classes * N * C > 0x7fffffffL)
+        return fail(SVAE_E_INVALID, "svae_class_sums_update: bad sizes B=%d N=%d C=%d n_classes=%d", B, N, C, n_classes);
+    if (!aligned || !label || !sum || !count) return fail(SVAE_E_INVALID, "svae_class_sums_update: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(class_sums_update_kernel, dim3(blocks_for((long)n_classes * N)), dim3(256), 0, st, aligned, cover, label, B, N,
+                       C, n_classes, sum, count);
+    return launch_status("svae_class_sums_update");
 }
 
 namespace {

@@ -239,6 +239,54 @@ def score_minibatch(script, x, y, p_net, q_net, *, num_samples, chunk, rotate, t
     return out
 
 
+POSES = ("iw", "best", "q")     # which estimate of an image's pose and content: the importance-weighted mean, the best sample, q's mean
+
+
+def _pose_rows(per_image, q_mu, pose):
+    """The (B, inf_dim) latent rows of one estimate out of what score_minibatch returned, in the decoder's units."""
+    if pose not in POSES:
+        raise RuntimeError("pose must be one of %s, got %r" % (POSES, pose))
+    inf_dim = q_mu.size(1)
+    return {"iw": per_image[:, 6:6 + inf_dim], "best": per_image[:, 6 + inf_dim:6 + 2 * inf_dim], "q": q_mu}[pose]
+
+
+@torch.no_grad()
+def align_minibatch(y, rows, cols, per_image, q_mu, rotate, translate, pose="iw", interp="bicubic"):
+    """The minibatch's observed images brought into the model's canonical frame (ops.align_images) at the pose estimate
+    `pose` (POSES) taken from score_minibatch's "per_image" and "q_mu": device slices, nothing is read back.  Returns (aligned,
+    shaped like y; cover (B, rows*cols) uint8).  A model with neither rotation nor translation gets its images back."""
+    lat = _pose_rows(per_image, q_mu, pose)
+    off = 1 if rotate else 0
+    theta = lat[:, 0].contiguous() if rotate else None
+    dx = lat[:, off:off + 2].contiguous() if translate else None
+    return ops.align_images(y, theta, dx, rows, cols, interp)
+
+
+def content_latents(per_image, q_mu, rotate, translate, pose="iw"):
+    """The content part (B, z_dim) of the same estimate: what reconstruct_unposed decodes."""
+    c0 = (1 if rotate else 0) + (2 if translate else 0)
+    return _pose_rows(per_image, q_mu, pose)[:, c0:].contiguous()
+
+
+def _decode_on_grid(x, p_net, B, zc):
+    """The decoder on the un-posed grid at the content latents zc."""
+    if hasattr(p_net, "forward_posed"):
+        return p_net.forward_posed(x, B, z=zc)
+    return p_net(x, zc)
+
+
+@torch.no_grad()
+def reconstruct_unposed(x, p_net, B, zc, gaussian_mean=False):
+    """The pose-free reconstruction at the content latents zc (B, z_dim) -> (B, N, C).  gaussian_mean (the particle scripts):
+    a decoder that also fits the noise (n_out == 2) keeps its mean only, which is the first N entries of each row (the layout
+    quirk of svae_gaussian_loglik)."""
+    out = _decode_on_grid(x, p_net, B, zc)
+    N = x.size(0)
+    if gaussian_mean and out.numel() == B * N * 2:
+        return out.reshape(B, -1)[:, :N].reshape(B, N, 1)
+    return out.reshape(B, N, -1)
+
+
 # ---------------------------------------------------------------- forward-only paths (image dumps of the training scripts)
 def _decode_unposed(x, y, p_net, q_net, rotate, translate, z_scale, use_cuda, noise):
     B = y.size(0)
@@ -249,9 +297,7 @@ def _decode_unposed(x, y, p_net, q_net, rotate, translate, z_scale, use_cuda, no
     r = noise if noise is not None else torch.empty(B, inf_dim, device=x.device, dtype=q_out.dtype).normal_()
     # sample z, then drop the rotation and translation slots: the image is drawn on the UNposed grid
     _, _, zc, _ = ops.latent_head(q_out, r, rotate, translate, False, 1.0, z_scale, math.pi)
-    if hasattr(p_net, "forward_posed"):
-        return p_net.forward_posed(x, B, z=zc)
-    return p_net(x, zc)
+    return _decode_on_grid(x, p_net, B, zc)
 
 
 @torch.no_grad()

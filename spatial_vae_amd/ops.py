@@ -50,7 +50,7 @@ def _p(t):
 
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
-                 for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES}.items()}
+                 for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -632,6 +632,65 @@ def rotate_augment(y, offset, rows, cols, quantize_u8):
     out = torch.empty_like(yc)
     _call("svae_rotate_bicubic", y.device, yc, out, mat_d, q_d, B, rows, cols, C, 1 if quantize_u8 else 0)
     return out.view_as(y)
+
+
+def align_images(y, theta, dx, rows, cols, interp="bicubic"):
+    """Bring each observed image into the model's canonical frame (svae_align_images, include/svae_align.h): the image
+    resampled where the decoder's pose (theta (B) radians or None, dx (B, 2) in the decoder's units or None) maps its grid.
+    y: (B, rows*cols[, C]) fp32 on the device, the poses device tensors too (nothing is read back).  Returns (aligned, a new
+    tensor shaped like y; cover (B, rows*cols) uint8, 1 where the observed image covers the pixel, whose value is 0 otherwise)."""
+    _require_hip(y, "y")
+    if interp not in _lib.ALIGN_INTERP:
+        raise RuntimeError("align_images: interp must be one of %s, got %r" % (sorted(_lib.ALIGN_INTERP), interp))
+    B = y.size(0)
+    yc = _f32(y)
+    C = yc.numel() // (B * rows * cols) if B * rows * cols else 0
+    if C * B * rows * cols != yc.numel() or C < 1:
+        raise RuntimeError("align_images: y %s does not hold %d images of %dx%d" % (tuple(y.shape), B, rows, cols))
+    for name, t, n in (("theta", theta, B), ("dx", dx, 2 * B)):
+        if t is not None:
+            _require_hip(t, name)
+            if t.numel() != n:
+                raise RuntimeError("align_images: %s has %d elements, %d expected for %d images" % (name, t.numel(), n, B))
+    theta, dx = _f32(theta), _f32(dx)
+    out = torch.empty_like(yc)
+    cover = torch.empty(B, rows * cols, dtype=torch.uint8, device=y.device)
+    _call("svae_align_images", y.device, yc, theta, dx, B, rows, cols, C, _lib.ALIGN_INTERP[interp], out, cover)
+    return out.view_as(y), cover
+
+
+class ClassSums:
+    """Per-class sums of aligned images (svae_class_sums_update): update() adds one minibatch -- aligned (B, N[, C]) and cover
+    (B, N) or None as align_images returns them, label (B) int32 on the device, -1 = in no class --, result() gives (sum
+    (n_classes, N, C), count (n_classes, N)), float64 on the device.  Images are added in the order they are handed over, without
+    atomics: the same sequence of updates gives the same bits."""
+
+    def __init__(self, n_classes, N, C, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("spatial_vae_amd: ClassSums must live on a HIP device (got %s); the MI355X path has no CPU "
+                               "fallback" % device)
+        self.n_classes, self.N, self.C, self.device = int(n_classes), int(N), int(C), device
+        if self.n_classes < 1 or self.N < 1 or self.C < 1:
+            raise RuntimeError("ClassSums: bad n_classes = %d, N = %d or C = %d" % (self.n_classes, self.N, self.C))
+        self.sum = torch.zeros(self.n_classes, self.N, self.C, dtype=torch.float64, device=device)
+        self.count = torch.zeros(self.n_classes, self.N, dtype=torch.float64, device=device)
+
+    def update(self, aligned, cover, label):
+        for name, t in (("aligned", aligned), ("cover", cover), ("label", label)):
+            if t is not None:
+                _require_hip(t, name)
+        B = label.numel()
+        aligned = _f32(aligned)
+        if label.dtype != torch.int32 or (cover is not None and cover.dtype != torch.uint8):
+            raise RuntimeError("ClassSums.update: label must be int32 and cover uint8")
+        if aligned.numel() != B * self.N * self.C or (cover is not None and cover.numel() != B * self.N):
+            raise RuntimeError("ClassSums.update: aligned %s / cover %s do not hold %d images of %d pixels, %d channels"
+                               % (tuple(aligned.shape), None if cover is None else tuple(cover.shape), B, self.N, self.C))
+        _call("svae_class_sums_update", self.device, aligned, cover, label, B, self.N, self.C, self.n_classes, self.sum, self.count)
+
+    def result(self):
+        return self.sum, self.count
 
 
 def ctf_filter(table, n, m, scale=1.0, device=None):
