@@ -685,7 +685,7 @@ int use_dense4(const Geo& g, int resid, int lastd) {
     return (nt2_ok && wgs2 >= 2048) ? 2 : 1;
 }
 
-template <int NT, bool DGRAD, bool FIRST, int LASTD, int CF>
+template <int NT, bool DGRAD, bool FIRST, int LASTD, int CF, bool DC = true>
 void launch_dense4_v(const DenseArgs& a, long groups, long set0, long nsets, hipStream_t st) {
     const dim3 grid((unsigned)(((nsets + 7) / 8) * 8 * ((a.Hp / 32) / NT)));
     // LDS: the two weight buffers, and for FIRST 3 x 128 floats per wave of per-row operands behind them
@@ -693,7 +693,7 @@ void launch_dense4_v(const DenseArgs& a, long groups, long set0, long nsets, hip
     // the grid is padded to whole XCD octets of sets: row groups beyond this launch's sets are dead in it (they belong to the
     // other launch of a split layer, or do not exist)
     const long gend = (set0 + nsets) * 4 < groups ? (set0 + nsets) * 4 : groups;
-    launch_gemm(dense4_kernel<NT, DGRAD, FIRST, LASTD, CF>, grid, dim3(256), (unsigned)lds, st, a, gend, set0);
+    launch_gemm(dense4_kernel<NT, DGRAD, FIRST, LASTD, CF, DC>, grid, dim3(256), (unsigned)lds, st, a, gend, set0);
 }
 
 // How a hidden-layer GEMM was launched: column tiles per workgroup (its partial results -- a.lpart, a.dfpart -- come per column
@@ -732,18 +732,21 @@ long dense4_main_sets(const Geo& g, long sets, bool tail_ok) {
 }
 
 // wide workgroups over the sets [0, main_sets), half-width ones over [main_sets, sets): one launch (dense4_dual_kernel)
-template <bool DGRAD, bool FIRST, int LASTD, int CF>
+template <bool DGRAD, bool FIRST, int LASTD, int CF, bool DC = true>
 void launch_dense4_dual(const DenseArgs& a, long groups, long sets, long main_sets, hipStream_t st) {
     const unsigned ntile = (unsigned)(a.Hp / 32);
     const unsigned grid_main = (unsigned)(((main_sets + 7) / 8) * 8) * (ntile / 2);
     const unsigned grid_tail = (unsigned)(((sets - main_sets + 7) / 8) * 8) * ntile;
     constexpr int lds = DenseCfg<2>::LDS_BYTES + (FIRST ? 4 * 3 * 128 * 4 : 0);
-    launch_gemm(dense4_dual_kernel<DGRAD, FIRST, LASTD, CF>, dim3(grid_main + grid_tail), dim3(256), (unsigned)lds, st, a, groups,
+    launch_gemm(dense4_dual_kernel<DGRAD, FIRST, LASTD, CF, DC>, dim3(grid_main + grid_tail), dim3(256), (unsigned)lds, st, a, groups,
                 main_sets, grid_main);
 }
 
+// dcoords (first only): the FIRST epilogue also leaves the per-row d(coords) partials in a.dfpart.  false = nobody reads them
+// (no caller asked for d(coords)): the dense4 kernels then run the epilogue form without them; dense_kernel writes them anyway.
 template <bool DGRAD>
-DenseBlocks launch_dense(const Geo& g, const DenseArgs& a, hipStream_t st, bool first = false, int lastd = 0, int cf = 0) {
+DenseBlocks launch_dense(const Geo& g, const DenseArgs& a, hipStream_t st, bool first = false, int lastd = 0, int cf = 0,
+                         bool dcoords = true) {
     took(DGRAD ? P_DENSE_FP32_DGRAD : P_DENSE_FP32_FWD);
     if (lastd) took(lastd == 1 ? P_OUT_BWD_FUSED_GENERIC : P_OUT_BWD_RANK1);
     Scope prof(DGRAD ? K_DENSE_DGRAD : K_DENSE_FWD, st, true);
@@ -765,9 +768,13 @@ DenseBlocks launch_dense(const Geo& g, const DenseArgs& a, hipStream_t st, bool 
                 }
             } else {
                 if (first) {
-                    if (lastd == 2) launch_dense4_v<NT, true, true, 2, 0>(a, groups, set0, nsets, st);
-                    else if (lastd == 3) launch_dense4_v<NT, true, true, 3, 0>(a, groups, set0, nsets, st);
-                    else launch_dense4_v<NT, true, true, 0, 0>(a, groups, set0, nsets, st);
+                    auto with = [&](auto dc_tag) {
+                        constexpr bool DC = decltype(dc_tag)::value;
+                        if (lastd == 2) launch_dense4_v<NT, true, true, 2, 0, DC>(a, groups, set0, nsets, st);
+                        else if (lastd == 3) launch_dense4_v<NT, true, true, 3, 0, DC>(a, groups, set0, nsets, st);
+                        else launch_dense4_v<NT, true, true, 0, 0, DC>(a, groups, set0, nsets, st);
+                    };
+                    if (dcoords) with(std::true_type()); else with(std::false_type());
                 } else {
                     if (lastd == 2) launch_dense4_v<NT, true, false, 2, 0>(a, groups, set0, nsets, st);
                     else if (lastd == 3) launch_dense4_v<NT, true, false, 3, 0>(a, groups, set0, nsets, st);
@@ -797,9 +804,13 @@ DenseBlocks launch_dense(const Geo& g, const DenseArgs& a, hipStream_t st, bool 
             }
         } else {
             if (first) {
-                if (lastd == 2) launch_dense4_dual<true, true, 2, 0>(a, groups, sets, main_sets, st);
-                else if (lastd == 3) launch_dense4_dual<true, true, 3, 0>(a, groups, sets, main_sets, st);
-                else launch_dense4_dual<true, true, 0, 0>(a, groups, sets, main_sets, st);
+                auto with = [&](auto dc_tag) {
+                    constexpr bool DC = decltype(dc_tag)::value;
+                    if (lastd == 2) launch_dense4_dual<true, true, 2, 0, DC>(a, groups, sets, main_sets, st);
+                    else if (lastd == 3) launch_dense4_dual<true, true, 3, 0, DC>(a, groups, sets, main_sets, st);
+                    else launch_dense4_dual<true, true, 0, 0, DC>(a, groups, sets, main_sets, st);
+                };
+                if (dcoords) with(std::true_type()); else with(std::false_type());
             } else {
                 if (lastd == 2) launch_dense4_dual<true, false, 2, 0>(a, groups, sets, main_sets, st);
                 else if (lastd == 3) launch_dense4_dual<true, false, 3, 0>(a, groups, sets, main_sets, st);
@@ -1153,6 +1164,13 @@ int svae_decoder_backward(const svae_desc* d, const svae_params* p, const svae_p
     bool fused_first = false;
     bool tail_pending = false;
     WgradReduceArgs tail_r{};
+    // the reduction of dW_o / db_o behind the fused forms' weight gradient waits for the tail launch too (nine blocks at the
+    // launch floor otherwise); without a tail launch it runs on its own behind the loop
+    bool obr_pending = false;
+    OutBwdReduceArgs tail_o{};
+    // d(coords) per row leaves the FIRST epilogue only for a caller that asked for d(coords) itself: dtheta / ddx follow from
+    // the per-image sums (first_layer_image_block, role 0)
+    const bool dcoords_wanted = pg && pg->dcoords;
     DenseBlocks fb{dense_nt_first(g.ntile), (long)g.Mp, 1};  // how the fp32 launch that ran the FIRST epilogue was blocked
     for (int l = g.L - 1; l >= 1; --l) {
         const bool last = fused_out && l == g.L - 1;
@@ -1196,9 +1214,10 @@ int svae_decoder_backward(const svae_desc* d, const svae_params* p, const svae_p
             if (db_elsewhere && grads->hidden_b[l - 1])
                 hipLaunchKernelGGL(colsum_reduce_kernel, dim3(g.Hp / 32), dim3(256), 0, st, pl.hbpart, grads->hidden_b[l - 1],
                                    g.H, g.Hp, ob_nparts);
-            if (last)
-                hipLaunchKernelGGL(out_bwd_reduce_kernel, dim3(g.C * ((g.Hp + 63) / 64) + 1), dim3(1024), 0, st, pl.wpart, pl.bpart,
-                                   grads->out_w, grads->out_b, g.C, g.H, g.Hp, pl.wg_S * 2);
+            if (last) {
+                tail_o = OutBwdReduceArgs{pl.wpart, pl.bpart, grads->out_w, grads->out_b, g.C, g.H, g.Hp, pl.wg_S * 2};
+                obr_pending = true;
+            }
         }
         DenseArgs a;
         a.in = last ? pl.act[l] : pl.dh[cur];
@@ -1219,7 +1238,8 @@ int svae_decoder_backward(const svae_desc* d, const svae_params* p, const svae_p
             launch_split_dgrad(g, pl, pl.dh[cur], p->hidden_w[l - 1], pl.act[l - 1], pl.dh[cur ^ 1], resid != 0, fused_first, pa,
                                split_ob && l == g.L - 1, st);
         else {
-            const DenseBlocks used = launch_dense<true>(g, a, st, fused_first, last ? (r1 ? (g.act == SVAE_ACT_TANH ? 2 : 3) : 1) : 0);
+            const DenseBlocks used = launch_dense<true>(g, a, st, fused_first, last ? (r1 ? (g.act == SVAE_ACT_TANH ? 2 : 3) : 1) : 0,
+                                                        0, dcoords_wanted);
             if (l == 1) fb = used;
         }
         cur ^= 1;
@@ -1229,6 +1249,13 @@ int svae_decoder_backward(const svae_desc* d, const svae_params* p, const svae_p
         tail_pending = false;
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((long)g.H * g.H + 63) / 64)), dim3(256), 0, st, tail_r);
     }
+    const unsigned obr_blocks = (unsigned)(g.C * ((g.Hp + 63) / 64) + 1);
+    if (obr_pending && !tail_pending) {   // no tail launch to ride in
+        obr_pending = false;
+        Scope prof(K_SMALL_BWD, st);
+        hipLaunchKernelGGL(out_bwd_reduce_kernel, dim3(obr_blocks), dim3(1024), 0, st, tail_o.wpart, tail_o.bpart, tail_o.dWo,
+                           tail_o.dbo, tail_o.C, tail_o.H, tail_o.Hp, tail_o.nparts);
+    }
     // coordinate layer
     const bool bil = (g.flags & SVAE_FLAG_BILINEAR) != 0;
     const bool want_coords = pg && (pg->dcoords || pg->dtheta || pg->ddx);
@@ -1237,21 +1264,28 @@ int svae_decoder_backward(const svae_desc* d, const svae_params* p, const svae_p
         Scope prof_l0(K_LAYER0_BWD, st);
         const bool split_first = split_bwd && (g.L == 2 || split_chain_on());   // which kernel ran the FIRST epilogue
         const bool want_dz = dz && g.Zd > 0;
+        // grid pose, dtheta / ddx but not d(coords): the role-0 blocks form them from the per-image sums, whichever kernel
+        // ran the FIRST epilogue; nobody reads dfpart then
+        const bool pose_sums = fused_first && !pose->coords && !dcoords_wanted && pg && (pg->dtheta || pg->ddx);
+        const bool role1 = want_coords && !pose_sums;
         if (fused_first) {
             // dh0 was reduced inside the data-gradient GEMM's epilogue: only small fixed-order per-image sums remain
             const FirstLayerImageArgs fa{pl.sgtile, split_first ? 2 : 1, g.Timg, g.H, g.Hp, pl.sgimg, p->latent_w,
                                          bil ? p->bilinear_w : nullptr, want_dz ? dz : (float*)nullptr, g.Zd, g.in_dim, pl.dfpart,
                                          g.ntile / (split_first ? split_nt(g) : fb.nt), g.N, g.Npad, (long)g.Mp,
-                                         want_coords ? dc : (float*)nullptr, pose->grid, pl.posebuf,
+                                         role1 ? dc : (float*)nullptr, pose->grid, pl.posebuf,
                                          pg ? pg->dtheta : (float*)nullptr, pg ? pg->ddx : (float*)nullptr,
-                                         split_first ? (long)g.Mp : fb.m_split, g.ntile / fb.nt_tail};
-            const unsigned nimg = (unsigned)g.B * (want_coords ? 2u : 1u);
+                                         split_first ? (long)g.Mp : fb.m_split, g.ntile / fb.nt_tail,
+                                         pose_sums ? pl.tab : (const float*)nullptr};
+            const unsigned nimg = (unsigned)g.B * (role1 ? 2u : 1u);
             if (tail_pending) {
                 tail_pending = false;
-                hipLaunchKernelGGL(backward_tail_kernel, dim3(nimg + (unsigned)(((long)g.H * g.H + 63) / 64)), dim3(256), 0, st, fa,
-                                   tail_r, nimg, (int)g.B);
+                const unsigned nred = (unsigned)(((long)g.H * g.H + 63) / 64);
+                hipLaunchKernelGGL(backward_tail_kernel, dim3(nimg + nred + (obr_pending ? obr_blocks : 0u)), dim3(256), 0, st, fa,
+                                   tail_r, tail_o, nimg, nred, (int)g.B);
+                obr_pending = false;
             } else {
-                hipLaunchKernelGGL(first_layer_image_kernel, dim3(g.B, want_coords ? 2 : 1), dim3(256), 0, st, fa);
+                hipLaunchKernelGGL(first_layer_image_kernel, dim3(g.B, role1 ? 2 : 1), dim3(256), 0, st, fa);
             }
         } else {
             const float* dh0 = pl.dh[cur];

@@ -219,6 +219,16 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// the same for a double (fixed order: xor butterfly within the wave, then the four waves); red: 4 doubles
+__device__ __forceinline__ double block_sum256d(double v, double* red) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // sum over a block of up to 1024 threads (a whole number of waves); result valid in every thread.  red: 16 floats.
 __device__ __forceinline__ float block_sum_waves(float v, float* red) {
     v = wave_sum32(v);

@@ -51,6 +51,12 @@ __device__ __forceinline__ f32x4v rank1_actgrad(f32x4v x) {
     return r;
 }
 
+// a + b that no fp-contract setting may fuse with a product feeding it
+__device__ __forceinline__ float add_uncontracted(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 // Same arguments as dense_kernel (DenseArgs; a.resid must be 0); `groups` = Mp / 128 (the caller guarantees Mp % 128 == 0);
 // the launch covers the sets (4 row groups each) from set0 on: a layer may be split into a wide launch over the sets that fill
 // whole rounds of resident workgroups and a half-width launch over the rest (launch_dense in api.hip).
@@ -58,6 +64,10 @@ __device__ __forceinline__ f32x4v rank1_actgrad(f32x4v x) {
 //   FIRST  (DGRAD) data gradient into the coordinate layer: reduce instead of store (dense_kernel's FIRST epilogue)
 //   LASTD  0, or 2 (tanh) / 3 (sigmoid): the rank-1 output-layer form (DGRAD): `in` is a_{L-1}, rows scaled by do[m] in the epilogue
 //   CF     forward of the last hidden layer: the epilogue also contracts with W_o (CF = a.C channels) into a.lpart
+//   DC     (FIRST) the epilogue also forms the per-row d(coords) partials of its column block into a.dfpart.  Off when no
+//          caller asked for d(coords) itself: dtheta / ddx then follow from the per-image (G0, G1, S) sums alone
+//          (first_layer_image_block, role 0), and the epilogue drops two of its ~8 fma per accumulator element, 16 live
+//          registers, the table load, and one half_reduce16 + store per half pass
 // waves per SIMD the register allocation is sized for: 4 NT accumulator tiles of 16 registers + 64 row-operand registers
 template <int NT>
 struct Dense4Occ {
@@ -66,10 +76,11 @@ struct Dense4Occ {
 
 // The workgroup's program, shared by dense4_kernel (one block width per launch) and dense4_dual_kernel (both widths in one
 // launch); `bid` is the workgroup's index among those of its width.
-template <int NT, bool DGRAD, bool FIRST, int LASTD, int CF>
+template <int NT, bool DGRAD, bool FIRST, int LASTD, int CF, bool DC = true>
 __device__ __forceinline__ void dense4_body(const DenseArgs& a, long groups, long set0, unsigned bid) {
     static_assert(NT == 1 || NT == 2, "4 NT accumulator tiles: two waves per SIMD up to NT = 2");
     static_assert(!FIRST || DGRAD, "FIRST is a data-gradient epilogue");
+    static_assert(DC || FIRST, "DC = false: a form of the FIRST epilogue only");
     static_assert(LASTD == 0 || ((LASTD == 2 || LASTD == 3) && DGRAD), "LASTD: the rank-1 data-gradient forms only");
     static_assert(CF == 0 || (!DGRAD && CF <= SVAE_MAX_OUT), "CF = output channels of the forward epilogue's W_o contraction");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -361,7 +372,7 @@ __device__ __forceinline__ void dense4_body(const DenseArgs& a, long groups, lon
             }
         } else {
             // FIRST: dh0 is reduced on the spot (dense_kernel's FIRST epilogue, per actual tile q of the group): over the tile's
-            // rows into (G0, G1, S) per feature, over this block's features into d(coords) per row.  Each tile goes in two
+            // rows into (G0, G1, S) per feature, over this block's features into d(coords) per row (DC only).  Each tile goes in two
             // half passes of 8 rows per lane (rows 16h + 8 rh + j, j = 0..7 <-> r = 2 rh + j/4, c = j % 4), which halves the
             // per-tile state and lets ONE half_reduce16 serve both coordinate components.  Per-row operands come from the
             // LDS area staged in the prologue; the a_0 vectors of the next half pass are loaded before this one is computed.
@@ -381,10 +392,10 @@ __device__ __forceinline__ void dense4_body(const DenseArgs& a, long groups, lon
                 const int q = hp >> 1, rh = hp & 1;
                 const long tile = rgl * 4 + q;
                 if (rh == 0) {
-                    const int b = (int)(tile / a.Timg);
+                    const int b = DC ? (int)(tile / a.Timg) : 0;
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
-                        w[t] = *reinterpret_cast<const float2*>(a.tab + ((long)b * Hp + nb * NB + t * 32 + nl) * kSlots);
+                        if constexpr (DC) w[t] = *reinterpret_cast<const float2*>(a.tab + ((long)b * Hp + nb * NB + t * 32 + nl) * kSlots);
                         sv[t] = 0.0f; g0[t] = 0.0f; g1[t] = 0.0f;
                     }
                 }
@@ -397,9 +408,11 @@ __device__ __forceinline__ void dense4_body(const DenseArgs& a, long groups, lon
                     x1v[r2] = *reinterpret_cast<const float4*>(rx + 128 + 4 * r2);
                     if (LASTD != 0) dq[r2] = *reinterpret_cast<const float4*>(rx + 256 + 4 * r2);
                 }
-                float pd[16];
+                float pd[16];   // DC only
+                if constexpr (DC) {
 #pragma unroll
-                for (int j = 0; j < 16; ++j) pd[j] = 0.0f;
+                    for (int j = 0; j < 16; ++j) pd[j] = 0.0f;
+                }
 #pragma unroll
                 for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -411,21 +424,28 @@ __device__ __forceinline__ void dense4_body(const DenseArgs& a, long groups, lon
 #pragma unroll
                         for (int cc = 0; cc < 4; ++cc) {
                             const int j = 4 * r2 + cc;
-                            sv[t] += vv[cc];
+                            // S adds the ROUNDED dh0 in either form: with the d(coords) terms the product behind vv has
+                            // many uses and hipcc keeps it apart; without them it would contract it into this sum
+                            // (v_fmac) and db_c, dW_z, dz would differ in the last bit between the two forms
+                            if constexpr (DC) sv[t] += vv[cc]; else sv[t] = add_uncontracted(sv[t], vv[cc]);
                             g0[t] += vv[cc] * xx0[cc];
                             g1[t] += vv[cc] * xx1[cc];
-                            pd[j] += vv[cc] * w[t].x;
-                            pd[8 + j] += vv[cc] * w[t].y;
+                            if constexpr (DC) {
+                                pd[j] += vv[cc] * w[t].x;
+                                pd[8 + j] += vv[cc] * w[t].y;
+                            }
                         }
                     }
                 // d(coords) of the 8 rows: this block's NB features = over the tiles (done) and the 32 lanes of the half-wave;
                 // lane class cls ends up with values 4 cls .. 4 cls + 3: component cls / 2 of rows 4 (cls % 2) .. + 3
-                float s4[4];
-                half_reduce16(pd, s4);
-                if (nl < 4) {
-                    const int cls = ((nl & 1) << 1) | (nl >> 1);
-                    float* dst = a.dfpart + ((long)nb * a.Mp + tile * 32 + 16 * h + 8 * rh + 4 * (cls & 1)) * 2 + (cls >> 1);
-                    dst[0] = s4[0]; dst[2] = s4[1]; dst[4] = s4[2]; dst[6] = s4[3];
+                if constexpr (DC) {
+                    float s4[4];
+                    half_reduce16(pd, s4);
+                    if (nl < 4) {
+                        const int cls = ((nl & 1) << 1) | (nl >> 1);
+                        float* dst = a.dfpart + ((long)nb * a.Mp + tile * 32 + 16 * h + 8 * rh + 4 * (cls & 1)) * 2 + (cls >> 1);
+                        dst[0] = s4[0]; dst[2] = s4[1]; dst[4] = s4[2]; dst[6] = s4[3];
+                    }
                 }
                 if (rh == 1) {
 #pragma unroll
@@ -448,9 +468,9 @@ __device__ __forceinline__ void dense4_body(const DenseArgs& a, long groups, lon
     }
 }
 
-template <int NT, bool DGRAD, bool FIRST, int LASTD, int CF>
+template <int NT, bool DGRAD, bool FIRST, int LASTD, int CF, bool DC = true>
 __global__ __launch_bounds__(256, Dense4Occ<NT>::value) void dense4_kernel(DenseArgs a, long groups, long set0) {
-    dense4_body<NT, DGRAD, FIRST, LASTD, CF>(a, groups, set0, blockIdx.x);
+    dense4_body<NT, DGRAD, FIRST, LASTD, CF, DC>(a, groups, set0, blockIdx.x);
 }
 
 // Both block widths in ONE launch: workgroups [0, grid_main) run 64-column blocks over the sets [0, sets_main), the rest
@@ -459,13 +479,13 @@ __global__ __launch_bounds__(256, Dense4Occ<NT>::value) void dense4_kernel(Dense
 // grid_main is a multiple of 8, so a workgroup's XCD label (id mod 8) is the same in both numberings.  Registers and LDS are
 // the wide form's (two workgroups per CU for either width); sets_main = all sets and no further workgroups is the plain wide
 // launch.
-template <bool DGRAD, bool FIRST, int LASTD, int CF>
+template <bool DGRAD, bool FIRST, int LASTD, int CF, bool DC = true>
 __global__ __launch_bounds__(256, 2) void dense4_dual_kernel(DenseArgs a, long groups, long sets_main, unsigned grid_main) {
     if (blockIdx.x < grid_main) {
         const long gmain = sets_main * 4 < groups ? sets_main * 4 : groups;
-        dense4_body<2, DGRAD, FIRST, LASTD, CF>(a, gmain, 0, blockIdx.x);
+        dense4_body<2, DGRAD, FIRST, LASTD, CF, DC>(a, gmain, 0, blockIdx.x);
     } else {
-        dense4_body<1, DGRAD, FIRST, LASTD, CF>(a, groups, sets_main, blockIdx.x - grid_main);
+        dense4_body<1, DGRAD, FIRST, LASTD, CF, DC>(a, groups, sets_main, blockIdx.x - grid_main);
     }
 }
 

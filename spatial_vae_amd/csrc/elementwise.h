@@ -340,48 +340,91 @@ __global__ void out_bwd_kernel(const float* __restrict__ a, const float* __restr
 // thread sums its parts in 8 interleaved chains, and the 16 lanes of a column are combined through LDS in a fixed order
 // (r01: 32 columns x 8 lanes with one chain per thread -- 64 dependent loads -- took 33 us for 512 parts).
 constexpr int kObrLanes = 16;
+struct OutBwdReduceArgs {
+    const float* wpart;
+    const float* bpart;
+    float* dWo;
+    float* dbo;
+    int C, H, Hp, nparts;
+};
+// One block's share (bx = block index among C * ceil(Hp / 64) + 1), for a block of 1024 / LPT threads: a thread carries the
+// part lanes (threadIdx.x >> 6) + (kObrLanes / LPT) j, j < LPT, each summed exactly as a thread of the 1024-thread form sums
+// its one lane, so the result does not depend on LPT (backward_tail_kernel runs these blocks with 256 threads: LPT = 4).
+template <int LPT>
+__device__ __forceinline__ void out_bwd_reduce_block(const OutBwdReduceArgs& a, unsigned bx, float (*red)[65]) {
+    static_assert(kObrLanes % LPT == 0, "whole part lanes per thread");
+    constexpr int LSTEP = kObrLanes / LPT;
+    const float* __restrict__ wpart = a.wpart;
+    const float* __restrict__ bpart = a.bpart;
+    const int C = a.C, H = a.H, Hp = a.Hp, nparts = a.nparts;
+    const int col = threadIdx.x & 63, pl0 = threadIdx.x >> 6;
+    const int blocks_per_c = (Hp + 63) / 64;
+    if (bx == (unsigned)(C * blocks_per_c)) {  // last block: the C bias gradients, same lane scheme over bpart
+#pragma unroll
+        for (int l = 0; l < LPT; ++l) {
+            const int pl = pl0 + LSTEP * l;
+            float s = 0.0f;
+            if (col < C)
+                for (int i = pl; i < nparts; i += kObrLanes) s += bpart[(long)i * C + col];
+            red[pl][col] = s;
+        }
+        __syncthreads();
+        if (pl0 == 0 && col < C && a.dbo) {
+            float t = red[0][col];
+#pragma unroll
+            for (int j = 1; j < kObrLanes; ++j) t += red[j][col];
+            a.dbo[col] = t;
+        }
+        return;
+    }
+    const int c = bx / blocks_per_c, n = (bx % blocks_per_c) * 64 + col;
+    float s[LPT];
+#pragma unroll
+    for (int l = 0; l < LPT; ++l) s[l] = 0.0f;
+    if (n < Hp) {
+        const float* p = wpart + (long)c * Hp + n;
+        const long st = (long)C * Hp;
+        float ch[LPT][8];
+        int i[LPT];
+#pragma unroll
+        for (int l = 0; l < LPT; ++l) {
+            i[l] = pl0 + LSTEP * l;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ch[l][j] = 0.0f;
+        }
+        // the lanes of a thread advance together (8 LPT loads in flight); a lane's own order is that of the LPT = 1 form
+        for (bool any = true; any;) {
+            any = false;
+#pragma unroll
+            for (int l = 0; l < LPT; ++l)
+                if (i[l] + 7 * kObrLanes < nparts) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) ch[l][j] += p[(long)(i[l] + j * kObrLanes) * st];
+                    i[l] += 8 * kObrLanes;
+                    any = true;
+                }
+        }
+#pragma unroll
+        for (int l = 0; l < LPT; ++l) {
+            for (; i[l] < nparts; i[l] += kObrLanes) ch[l][0] += p[(long)i[l] * st];
+            s[l] = ((ch[l][0] + ch[l][1]) + (ch[l][2] + ch[l][3])) + ((ch[l][4] + ch[l][5]) + (ch[l][6] + ch[l][7]));
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < LPT; ++l) red[pl0 + LSTEP * l][col] = s[l];
+    __syncthreads();
+    if (pl0 == 0 && n < H && a.dWo) {
+        float t = red[0][col];
+#pragma unroll
+        for (int j = 1; j < kObrLanes; ++j) t += red[j][col];
+        a.dWo[(long)c * H + n] = t;
+    }
+}
 __global__ void __launch_bounds__(1024) out_bwd_reduce_kernel(const float* __restrict__ wpart, const float* __restrict__ bpart,
                                                               float* __restrict__ dWo, float* __restrict__ dbo, int C, int H,
                                                               int Hp, int nparts) {
     __shared__ float red[kObrLanes][65];
-    const int col = threadIdx.x & 63, pl = threadIdx.x >> 6;
-    const int blocks_per_c = (Hp + 63) / 64;
-    if (blockIdx.x == (unsigned)(C * blocks_per_c)) {  // last block: the C bias gradients, same lane scheme over bpart
-        float s = 0.0f;
-        if (col < C)
-            for (int i = pl; i < nparts; i += kObrLanes) s += bpart[(long)i * C + col];
-        red[pl][col] = s;
-        __syncthreads();
-        if (pl == 0 && col < C && dbo) {
-            float t = red[0][col];
-#pragma unroll
-            for (int j = 1; j < kObrLanes; ++j) t += red[j][col];
-            dbo[col] = t;
-        }
-        return;
-    }
-    const int c = blockIdx.x / blocks_per_c, n = (blockIdx.x % blocks_per_c) * 64 + col;
-    float s = 0.0f;
-    if (n < Hp) {
-        const float* p = wpart + (long)c * Hp + n;
-        const long st = (long)C * Hp;
-        float ch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int i = pl;
-        for (; i + 7 * kObrLanes < nparts; i += 8 * kObrLanes) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ch[j] += p[(long)(i + j * kObrLanes) * st];
-        }
-        for (; i < nparts; i += kObrLanes) ch[0] += p[(long)i * st];
-        s = ((ch[0] + ch[1]) + (ch[2] + ch[3])) + ((ch[4] + ch[5]) + (ch[6] + ch[7]));
-    }
-    red[pl][col] = s;
-    __syncthreads();
-    if (pl == 0 && n < H && dWo) {
-        float t = red[0][col];
-#pragma unroll
-        for (int j = 1; j < kObrLanes; ++j) t += red[j][col];
-        dWo[(long)c * H + n] = t;
-    }
+    out_bwd_reduce_block<1>(OutBwdReduceArgs{wpart, bpart, dWo, dbo, C, H, Hp, nparts}, blockIdx.x, red);
 }
 
 // ---------------------------------------------------------------- coordinate layer, backward
@@ -488,6 +531,14 @@ __global__ void layer0_bwd_coords_kernel(PoseArgs pose, const float4* __restrict
 //      are per-image, fixed-order sums, done by ONE launch of B x 2 blocks instead of four kernels:
 //        role 0 (blockIdx.y == 0): sgimg[b][k] = sum over the image's tiles (and halves); then dz[b][q] from it (d);
 //        role 1 (blockIdx.y == 1): d(coords)[b][i] = sum over column blocks; then dtheta[b], ddx[b] from it (e).
+//      When d(coords) itself is not asked for (`tab` set, no role-1 blocks), role 0 also forms dtheta[b] and ddx[b], from
+//      the per-image sums alone.  With x0'' = c g0 - s g1 + dx0, x1'' = s g0 + c g1 + dx1 (posebuf[b] = (c, s, dx0, dx1)):
+//      d(x0'')/d(theta) = -(x1'' - dx1), d(x1'')/d(theta) = x0'' - dx0, and d(coords)[i] = sum_k dh0[i][k] (w0[k], w1[k]) with
+//      (w0, w1) = tab[b][k][0..1], so
+//        ddx[b]    = ( sum_k w0[k] S[k],  sum_k w1[k] S[k] )
+//        dtheta[b] =   sum_k ( w1[k] (G0[k] - dx0 S[k])  -  w0[k] (G1[k] - dx1 S[k]) )
+//      -- three H-length sums in a fixed order (no atomics) in place of d(coords) per row and column block, accumulated in
+//      double from the per-tile sums on.
 struct FirstLayerImageArgs {
     const float* sgtile;
     int nhalf, Timg, H, Hp;
@@ -506,8 +557,9 @@ struct FirstLayerImageArgs {
     float* ddx;
     long m_split;
     int nblocks_tail;
+    const float* tab;   // role 0 forms dtheta / ddx from sgimg and this table (in_dim == 2); NULL: role 1 does, from d(coords)
 };
-// one block's share: image b, role 0 (sgimg, dz) or 1 (d(coords), dtheta, ddx); `red` is 4 floats of LDS
+// one block's share: image b, role 0 (sgimg, dz) or 1 (d(coords), dtheta, ddx); `red` is 8 floats of LDS, 8-byte aligned
 __device__ __forceinline__ void first_layer_image_block(const FirstLayerImageArgs& a, int b, int role, float* red) {
     const float* __restrict__ sgtile = a.sgtile;
     const int nhalf = a.nhalf, Timg = a.Timg, H = a.H, Hp = a.Hp;
@@ -528,23 +580,39 @@ __device__ __forceinline__ void first_layer_image_block(const FirstLayerImageArg
     const int nblocks_tail = a.nblocks_tail;
 
     if (role == 0) {
+        // pose gradients from the sums (see above): the image's tile sums are also added up in double, and so are the three
+        // H-long sums over k -- dtheta is what is left of terms w G that cancel to a small fraction of their size, and in
+        // fp32 the rounding of the per-image sums would show in it (sgimg itself keeps its fp32 sums and bits)
+        const bool pose_sums = a.tab && (dtheta || ddx);
+        double pt = 0.0, p0 = 0.0, p1 = 0.0;
+        float4 pb = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+        if (pose_sums) pb = posebuf[b];
         for (int k = threadIdx.x; k < Hp; k += 256) {
             // the image's Timg * nhalf partial rows, 8 loads in flight (fixed order: chain j takes rows j, j+8, ...)
             const float* src = sgtile + ((long)b * Timg * nhalf * Hp + k) * 4;
             const long rst = (long)Hp * 4;
             const int rows = Timg * nhalf;
             float c0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            double d0 = 0.0, d1 = 0.0, d2 = 0.0;
             int r = 0;
             for (; r + 7 < rows; r += 8) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const float4 v = *reinterpret_cast<const float4*>(src + (r + j) * rst);
                     c0[j] += v.x; c1[j] += v.y; c2[j] += v.z;
+                    if (pose_sums) { d0 += (double)v.x; d1 += (double)v.y; d2 += (double)v.z; }
                 }
             }
             for (int j = 0; r < rows; ++r, ++j) {
                 const float4 v = *reinterpret_cast<const float4*>(src + r * rst);
                 c0[j] += v.x; c1[j] += v.y; c2[j] += v.z;
+                if (pose_sums) { d0 += (double)v.x; d1 += (double)v.y; d2 += (double)v.z; }
+            }
+            if (pose_sums && k < H) {
+                const float2 w = *reinterpret_cast<const float2*>(a.tab + ((long)b * Hp + k) * kSlots);
+                p0 += (double)w.x * d2;
+                p1 += (double)w.y * d2;
+                pt += (double)w.y * (d0 - (double)pb.z * d2) - (double)w.x * (d1 - (double)pb.w * d2);
             }
             const float g0 = ((c0[0] + c0[1]) + (c0[2] + c0[3])) + ((c0[4] + c0[5]) + (c0[6] + c0[7]));
             const float g1 = ((c1[0] + c1[1]) + (c1[2] + c1[3])) + ((c1[4] + c1[5]) + (c1[6] + c1[7]));
@@ -552,6 +620,19 @@ __device__ __forceinline__ void first_layer_image_block(const FirstLayerImageArg
             float4* dst = reinterpret_cast<float4*>(sgimg + ((long)b * Hp + k) * kSlots);
             dst[0] = make_float4(g0, g1, 0.0f, 0.0f);
             dst[1] = make_float4(0.0f, sv, 0.0f, 0.0f);
+        }
+        if (pose_sums) {
+            double* redd = reinterpret_cast<double*>(red);
+            pt = block_sum256d(pt, redd);
+            p0 = block_sum256d(p0, redd);
+            p1 = block_sum256d(p1, redd);
+            if (threadIdx.x == 0) {
+                if (dtheta) dtheta[b] = (float)pt;
+                if (ddx) {
+                    ddx[2 * b] = (float)p0;
+                    ddx[2 * b + 1] = (float)p1;
+                }
+            }
         }
         if (!dz || Zd <= 0) return;
         // dz[b][q] = sum_k S_b[k] W_z[k][q] + sum_{k,p} G_b[k][p] W_bi[k][p][q]; every thread re-reads what it wrote itself
@@ -603,16 +684,20 @@ __device__ __forceinline__ void first_layer_image_block(const FirstLayerImageArg
 }
 
 __global__ void __launch_bounds__(256) first_layer_image_kernel(FirstLayerImageArgs a) {
-    __shared__ float red[4];
+    __shared__ __attribute__((aligned(8))) float red[8];
     first_layer_image_block(a, blockIdx.x, blockIdx.y, red);
 }
 // The same per-image blocks and the split-K reduction of the first hidden layer's weight gradient in ONE launch: both are
 // latency-bound (25.5 + 20.6 us at BASELINE cfg 2 as two launches) and independent of each other, so their blocks fill the
-// chip together.  Blocks [0, nimg) are (image, role) pairs, the rest wgrad_reduce blocks.
-__global__ void __launch_bounds__(256) backward_tail_kernel(FirstLayerImageArgs f, WgradReduceArgs r, unsigned nimg, int B) {
-    __shared__ float red[4][64];
-    if (blockIdx.x < nimg) first_layer_image_block(f, (int)(blockIdx.x % (unsigned)B), (int)(blockIdx.x / (unsigned)B), &red[0][0]);
-    else wgrad_reduce_block(r, blockIdx.x - nimg, red);
+// chip together.  Blocks [0, nimg) are (image, role) pairs, the next nred wgrad_reduce blocks, and what remains (none, or
+// o.C * ceil(o.Hp / 64) + 1) are the blocks of the output layer's reduction (out_bwd_reduce_block, four part lanes per
+// thread: the sums and their order are those of out_bwd_reduce_kernel), which otherwise is one more launch at the floor.
+__global__ void __launch_bounds__(256) backward_tail_kernel(FirstLayerImageArgs f, WgradReduceArgs r, OutBwdReduceArgs o,
+                                                            unsigned nimg, unsigned nred, int B) {
+    __shared__ __attribute__((aligned(8))) float red[kObrLanes * 65];
+    if (blockIdx.x < nimg) first_layer_image_block(f, (int)(blockIdx.x % (unsigned)B), (int)(blockIdx.x / (unsigned)B), red);
+    else if (blockIdx.x < nimg + nred) wgrad_reduce_block(r, blockIdx.x - nimg, reinterpret_cast<float (*)[64]>(red));
+    else out_bwd_reduce_block<4>(o, blockIdx.x - nimg - nred, reinterpret_cast<float (*)[65]>(red));
 }
 
 // (c) first-layer parameter gradients from the per-image sums.  A block owns 16 consecutive (k, slot) columns of sgimg;
