@@ -136,6 +136,19 @@ ALIGN_SIGNATURES = {
 ALIGN_INTERP = {"bilinear": 0, "bicubic": 1}
 
 
+# ---- include/svae_ctfcorr.h: CTF correction in Fourier space, a fourth header with a table of its own ----
+# Same rules once more (tests/test_ctfcorr_cpu.py holds these rows to that header's prototypes).  The header's two constants are
+# the values of CTF_MODE, under SVAE_CTF_<NAME>.
+CTFCORR_SIGNATURES = {
+    "svae_ctf_apply_workspace_bytes": (sz, [i32, i32, i32]),
+    "svae_ctf_apply": (cint, [vp, vp, i32, i32, i32, f64, i32, vp, vp, sz, vp]),
+    "svae_ctf_power_update": (cint, [vp, vp, i32, i32, i32, f64, i32, vp, vp]),
+    "svae_wiener_finish_workspace_bytes": (sz, [i32, i32, i32]),
+    "svae_wiener_finish": (cint, [vp, vp, f64, i32, i32, i32, vp, vp, sz, vp]),
+}
+CTF_MODE = {"flip": 0, "multiply": 1}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -158,7 +171,7 @@ def lib():
         raise RuntimeError("spatial_vae_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
-    for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

@@ -750,7 +750,7 @@ def infer_arguments(argv=None):
         p.add_argument("--" + name, default=None, help="instead of the path stored in the state file")
     p.add_argument("--aligned", metavar="PATH", help="also write every image brought into the model's canonical frame (its "
                    "pose removed), in dataset order: .npy = (images, rows, cols, C) float32, .mrcs = an MRC stack (one channel "
-                   "only).  The observed images resampled, nothing else: not CTF-corrected, not masked")
+                   "only).  The observed images resampled, nothing else: not masked, and CTF-corrected only under --ctf_correct flip")
     p.add_argument("--recon", metavar="PATH", help="also write every image's pose-free reconstruction (the decoder on the "
                    "un-posed grid at the image's content latents), same formats")
     p.add_argument("--class_averages", metavar="PATH.npz", help="also write the sums, counts and averages of the aligned images "
@@ -761,8 +761,29 @@ def infer_arguments(argv=None):
                    "decodes: the importance-weighted mean (iw, the default), the best sample, or q's mean")
     p.add_argument("--interp", choices=["bicubic", "bilinear"], default=None, help="resampling of --aligned / --class_averages "
                    "(default bicubic: Catmull-Rom)")
+    p.add_argument("--ctf_correct", choices=["flip", "wiener"], default=None, help="particles with a CTF table only: correct each "
+                   "observed image by its own transfer function H before it is aligned.  flip: multiply its Fourier coefficients "
+                   "by the sign of H; --aligned and the class averages then hold phase-flipped particles.  wiener: leave those as "
+                   "they are and add to --class_averages the Wiener averages sum(H y) / (sum(H^2) + lambda) per class, with their "
+                   "numerator and denominator.  Scoring is untouched either way")
+    p.add_argument("--wiener_lambda", type=float, default=None, metavar="X", help="with --ctf_correct wiener: the regulariser, "
+                   "X >= 0, the reciprocal of the per-particle spectral signal-to-noise ratio assumed (default 1.0: a convention, not "
+                   "a tuned value; the .npz keeps numerator and denominator, so another X needs no second run)")
     args = p.parse_args(argv)
     args.train_argv = train_argv
+    if args.ctf_correct is not None and args.script != "particles":
+        p.error("--ctf_correct is for particles (the script whose images have a CTF), not %s" % args.script)
+    if args.ctf_correct == "flip" and args.aligned is None and args.class_averages is None:
+        p.error("--ctf_correct flip needs one of --aligned, --class_averages")
+    if args.ctf_correct == "wiener" and args.class_averages is None:
+        p.error("--ctf_correct wiener needs --class_averages")
+    if args.wiener_lambda is not None:
+        if args.ctf_correct != "wiener":
+            p.error("--wiener_lambda needs --ctf_correct wiener")
+        if not 0 <= args.wiener_lambda < float("inf"):
+            p.error("--wiener_lambda must be a finite number >= 0 (got %r)" % args.wiener_lambda)
+    elif args.ctf_correct == "wiener":
+        args.wiener_lambda = 1.0
     if args.num_samples < 1:
         p.error("--num_samples must be >= 1")
     if not 1 <= args.chunk <= INFER_MAX_CHUNK:
@@ -968,6 +989,24 @@ def infer_main(args, parser_fn, build, positional=()):
         n_classes = max(int(labels.max()) + 1, 1) if images else 1
         sums = ops.ClassSums(n_classes, n * m, channels, device)
         label_d = torch.from_numpy(labels.astype(np.int32)).to(device)
+    # --ctf_correct: each image through its own transfer function (the table rows of the split, uploaded once) before it is aligned
+    correct = getattr(args, "ctf_correct", None)
+    table_d = wiener = None
+    if correct is not None:
+        table = cfg.get("ctf_params_" + args.split)
+        if table is None:
+            _refuse("--ctf_correct needs the CTF parameters of the {0} split: the run has no --ctf-{0} table".format(args.split))
+        if table.shape[0] < images:
+            _refuse("the CTF table of the {} split has {} rows, the split has {} images".format(args.split, table.shape[0], images))
+        if channels != 1:
+            _refuse("--ctf_correct takes one-channel images, these have {}".format(channels))
+        if rotate and n != m:
+            _refuse("--ctf_correct on a model that rotates needs a square box (the transfer function commutes with the rotation "
+                    "only there); these images are {}x{}".format(n, m))
+        table_d = torch.from_numpy(np.ascontiguousarray(table[:images], dtype=np.float64)).to(device)
+        ctf_scale = cfg["ctf_scale"]
+        if correct == "wiener":     # numerator: class sums of the aligned H*y; denominator: class sums of H^2
+            wiener = (ops.ClassSums(sums.n_classes, n * m, 1, device), ops.CtfPower(sums.n_classes, n, m, device, scale=ctf_scale))
     gen = torch.Generator()
     gen.manual_seed(args.seed)
     rows = []
@@ -979,7 +1018,13 @@ def infer_main(args, parser_fn, build, positional=()):
                                 mask=mask, ctf=None if ctf is None else ctf[lo:lo + bs], noise=noise)
         rows.append(torch.cat([out["per_image"], out["q_mu"], out["q_std"]], 1))
         if "aligned" in stacks or sums is not None:
-            aligned, cover = E.align_minibatch(y, n, m, out["per_image"], out["q_mu"], rotate, translate, args.pose, args.interp)
+            seen = y if correct != "flip" else ops.ctf_apply(y, table_d[lo:lo + bs], n, m, ctf_scale, "flip")
+            aligned, cover = E.align_minibatch(seen, n, m, out["per_image"], out["q_mu"], rotate, translate, args.pose, args.interp)
+            if wiener is not None:
+                g = ops.ctf_apply(y, table_d[lo:lo + bs], n, m, ctf_scale, "multiply")
+                g, g_cover = E.align_minibatch(g, n, m, out["per_image"], out["q_mu"], rotate, translate, args.pose, args.interp)
+                wiener[0].update(g, g_cover, label_d[lo:lo + bs])
+                wiener[1].update(table_d[lo:lo + bs], label_d[lo:lo + bs])
             if sums is not None:
                 sums.update(aligned, cover, label_d[lo:lo + bs])
             if "aligned" in stacks:
@@ -999,6 +1044,8 @@ def infer_main(args, parser_fn, build, positional=()):
             "mean_bound": means[0], "mean_loglik": means[1], "mean_kl": means[2]}
     if any(v is not None for v in want.values()):   # only then: without the options the file is what it always was
         meta.update(pose=args.pose, interp=args.interp, labels=args.labels, **want)
+    if correct is not None:
+        meta.update(ctf_correct=correct, wiener_lambda=args.wiener_lambda)
     arrays["meta"] = np.array(json.dumps(meta))
     for k, stack in stacks.items():
         write_stack(want[k], stack.numpy().reshape(images, n, m, channels))
@@ -1007,7 +1054,14 @@ def infer_main(args, parser_fn, build, positional=()):
         total, count = total.reshape(sums.n_classes, n, m, channels), count.reshape(sums.n_classes, n, m)
         average = np.divide(total, count[..., None], out=np.zeros_like(total), where=count[..., None] > 0).astype(np.float32)
         members = np.bincount(labels[labels >= 0], minlength=sums.n_classes).astype(np.int64)
-        write_npz(want["class_averages"], {"sum": total, "count": count, "average": average, "members": members})
+        classes = {"sum": total, "count": count, "average": average, "members": members}
+        if wiener is not None:      # numerator and denominator too: another lambda needs no second run
+            w_sum, w_den = wiener[0].result()[0], wiener[1].result()
+            w_avg = ops.wiener_finish(w_sum, w_den, args.wiener_lambda, n, m)
+            classes.update(wiener_sum=w_sum.cpu().numpy().reshape(sums.n_classes, n, m, 1), wiener_den=w_den.cpu().numpy(),
+                           wiener_average=w_avg.cpu().numpy().reshape(sums.n_classes, n, m, 1),
+                           wiener_lambda=np.float64(args.wiener_lambda))
+        write_npz(want["class_averages"], classes)
     write_npz(args.out, arrays)
     print("images {}\tbound {!r}\tlog p(x|z) {!r}\tKL {!r}\tmedian ESS {:.3f}".format(
         host.shape[0], means[0], means[1], means[2], float(np.median(arrays["ess"]))))

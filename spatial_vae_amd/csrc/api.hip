@@ -15,12 +15,14 @@
 #include "common.h"
 #include "../../include/svae_stream.h"
 #include "../../include/svae_align.h"
+#include "../../include/svae_ctfcorr.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
 #include "elementwise.h"
 #include "iw_stream.h"
 #include "align.h"
+#include "ctfcorr.h"
 #include "encoder.h"
 #include "split.h"
 
@@ -1771,6 +1773,92 @@ int svae_ctf_filter(const double* params, float* filters, int32_t count, int32_t
                            static_cast<double*>(ws));
     }
     return launch_status("svae_ctf_filter");
+}
+
+// ---- CTF correction in Fourier space (include/svae_ctfcorr.h) ----
+namespace {
+size_t dft_lds_bytes(int n, int m) { return ((size_t)n * m * 4 + 2 * ((size_t)n + m)) * sizeof(double); }
+size_t dft_twiddle_bytes(int n, int m) { return 2 * ((size_t)n + m) * sizeof(double); }
+int dft_groups(int count) { return count < CTF_SCRATCH_GROUPS ? count : CTF_SCRATCH_GROUPS; }
+
+size_t dft_workspace_bytes(int count, int n, int m) {
+    if (count < 1 || n < 1 || m < 1) return 0;
+    if (dft_lds_bytes(n, m) <= CTF_LDS_MAX) return 0;  // both complex planes fit the LDS of one CU
+    return (size_t)dft_groups(count) * (size_t)n * m * 4 * sizeof(double);
+}
+
+// the plane-size and workspace rules svae_ctf_apply and svae_wiener_finish share; 0 or the refusal
+int dft_check(const char* who, int count, int n, int m, const void* ws, size_t ws_bytes) {
+    if (n < 2 || m < 2) return fail(SVAE_E_INVALID, "%s: planes must be at least 2 x 2 (got %d x %d)", who, n, m);
+    if (dft_twiddle_bytes(n, m) > CTF_LDS_MAX)
+        return fail(SVAE_E_INVALID, "%s: %d x %d planes are not supported (n + m must not exceed %zu)", who, n, m,
+                    CTF_LDS_MAX / (2 * sizeof(double)));
+    if ((long)count * n * m > 0x7fffffffL) return fail(SVAE_E_INVALID, "%s: %d planes of %d x %d are too many", who, count, n, m);
+    const size_t need = dft_workspace_bytes(count, n, m);
+    if (need && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255)))
+        return fail(SVAE_E_INVALID, "%s: %d x %d planes need a workspace of %zu bytes, 256-byte aligned (got %zu)", who, n, m, need,
+                    ws_bytes);
+    return SVAE_OK;
+}
+
+// launch one of the two plane kernels in its LDS or its workspace form
+extern "C++" template <class K, class... Args>
+int dft_launch(const char* who, K lds_kernel, K ws_kernel, int count, int n, int m, void* ws, hipStream_t st, Args... args) {
+    const size_t lds = dft_lds_bytes(n, m);
+    const bool scratch = lds > CTF_LDS_MAX;
+    const size_t bytes = scratch ? dft_twiddle_bytes(n, m) : lds;
+    K kernel = scratch ? ws_kernel : lds_kernel;
+    if (bytes > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)bytes) != hipSuccess)
+        return fail(SVAE_E_LAUNCH, "%s: cannot reserve %zu bytes of LDS", who, bytes);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(kernel, dim3(scratch ? dft_groups(count) : count), dim3(256), bytes, st, args...,
+                       static_cast<double*>(scratch ? ws : nullptr));
+    return launch_status(who);
+}
+}  // namespace
+
+size_t svae_ctf_apply_workspace_bytes(int32_t B, int32_t n, int32_t m) { return dft_workspace_bytes(B, n, m); }
+
+int svae_ctf_apply(const float* y, const double* params, int32_t B, int32_t n, int32_t m, double scale, int32_t mode, float* out,
+                   void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (B < 1) return fail(SVAE_E_INVALID, "svae_ctf_apply: B must be positive (got %d)", B);
+    if (mode != SVAE_CTF_FLIP && mode != SVAE_CTF_MULTIPLY) return fail(SVAE_E_INVALID, "svae_ctf_apply: unknown mode %d", mode);
+    if (!(scale > 0.0)) return fail(SVAE_E_INVALID, "svae_ctf_apply: scale must be positive");
+    if (const int rc = dft_check("svae_ctf_apply", B, n, m, ws, ws_bytes)) return rc;
+    const long total = (long)B * n * m;
+    if (!y || !out || !params) return fail(SVAE_E_INVALID, "svae_ctf_apply: null y, out or params");
+    if (y < out + total && out < y + total)
+        return fail(SVAE_E_INVALID, "svae_ctf_apply: y and out must be two buffers that do not overlap");
+    return dft_launch("svae_ctf_apply", ctf_apply_kernel<false>, ctf_apply_kernel<true>, B, n, m, ws,
+                      static_cast<hipStream_t>(stream), y, params, (int)B, (int)n, (int)m, scale, (int)mode, out);
+}
+
+int svae_ctf_power_update(const double* params, const int32_t* label, int32_t B, int32_t n, int32_t m, double scale,
+                          int32_t n_classes, double* den, svae_stream_t stream) {
+    if (B < 1 || n < 2 || m < 2 || n_classes < 1 || n_classes > 4096 || (long)n * m > 0x7fffffffL ||
+        (long)n_classes * n * m > 0x7fffffffL)
+        return fail(SVAE_E_INVALID, "svae_ctf_power_update: bad sizes B=%d n=%d m=%d n_classes=%d", B, n, m, n_classes);
+    if (!(scale > 0.0)) return fail(SVAE_E_INVALID, "svae_ctf_power_update: scale must be positive");
+    if (!params || !label || !den) return fail(SVAE_E_INVALID, "svae_ctf_power_update: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(ctf_power_update_kernel, dim3(blocks_for((long)n_classes * n * m)), dim3(256), 0, st, params, label, B, n, m,
+                       scale, n_classes, den);
+    return launch_status("svae_ctf_power_update");
+}
+
+size_t svae_wiener_finish_workspace_bytes(int32_t n_classes, int32_t n, int32_t m) { return dft_workspace_bytes(n_classes, n, m); }
+
+int svae_wiener_finish(const double* sum, const double* den, double lambda, int32_t n_classes, int32_t n, int32_t m, float* average,
+                       void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (n_classes < 1 || n_classes > 4096)
+        return fail(SVAE_E_INVALID, "svae_wiener_finish: n_classes %d outside 1..4096", n_classes);
+    if (!(lambda >= 0.0) || isinf(lambda)) return fail(SVAE_E_INVALID, "svae_wiener_finish: lambda must be finite and >= 0");
+    if (const int rc = dft_check("svae_wiener_finish", n_classes, n, m, ws, ws_bytes)) return rc;
+    if (!sum || !den || !average) return fail(SVAE_E_INVALID, "svae_wiener_finish: null sum, den or average");
+    return dft_launch("svae_wiener_finish", wiener_finish_kernel<false>, wiener_finish_kernel<true>, n_classes, n, m, ws,
+                      static_cast<hipStream_t>(stream), sum, den, lambda, (int)n_classes, (int)n, (int)m, average);
 }
 
 int svae_gemm_mode_set(int mode) {

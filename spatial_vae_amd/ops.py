@@ -50,7 +50,8 @@ def _p(t):
 
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
-                 for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES}.items()}
+                 for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES,
+                                             **_lib.CTFCORR_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -691,6 +692,88 @@ class ClassSums:
 
     def result(self):
         return self.sum, self.count
+
+
+def _ctf_rows(table, device, who):
+    """The (P, 8) float64 parameter table of spatial_vae/ctf.py:26-30 on `device`: a host array is uploaded, a device tensor
+    is taken as it is."""
+    tab = table if torch.is_tensor(table) else torch.from_numpy(np.array(table, dtype=np.float64, order="C"))
+    if tab.dim() != 2 or tab.size(1) != 8:
+        raise RuntimeError("%s: expected a (P, 8) parameter table, got %s" % (who, tuple(tab.shape)))
+    tab = tab.to(device=device, dtype=torch.float64).contiguous()
+    _require_hip(tab, "CTF table")
+    return tab
+
+
+def ctf_apply(y, table, n, m, scale=1.0, mode="flip"):
+    """Each observed image through its own transfer function in Fourier space (svae_ctf_apply, include/svae_ctfcorr.h):
+    mode "flip" multiplies every Fourier coefficient by the sign of H_i (phase flipping), "multiply" by H_i itself.  y: (B,
+    n*m) or (B, n, m) fp32 on the device, one channel; table: the (B, 8) parameters of the same images, a host array or a
+    float64 device tensor (nothing is read back).  Returns a new tensor shaped like y."""
+    _require_hip(y, "y")
+    if mode not in _lib.CTF_MODE:
+        raise RuntimeError("ctf_apply: mode must be one of %s, got %r" % (sorted(_lib.CTF_MODE), mode))
+    B = y.size(0)
+    yc = _f32(y)
+    if yc.numel() != B * n * m:
+        raise RuntimeError("ctf_apply: y %s does not hold %d one-channel images of %dx%d" % (tuple(y.shape), B, n, m))
+    tab = _ctf_rows(table, y.device, "ctf_apply")
+    if tab.size(0) != B:
+        raise RuntimeError("ctf_apply: %d rows of CTF parameters for %d images" % (tab.size(0), B))
+    out = torch.empty_like(yc)
+    ws_bytes = _lib.lib().svae_ctf_apply_workspace_bytes(B, n, m)      # 0 while the planes fit the LDS (up to 71 x 71)
+    ws = _buf(y.device, ws_bytes, "ctfcorr") if ws_bytes else None
+    _call("svae_ctf_apply", y.device, yc, tab, B, n, m, float(scale), _lib.CTF_MODE[mode], out, ws, ws_bytes)
+    return out.view_as(y)
+
+
+class CtfPower:
+    """Per-class sums of the squared transfer functions (svae_ctf_power_update), the denominator of a Wiener class average:
+    update() adds one minibatch -- table (B, 8) as for ctf_apply, label (B) int32 on the device, -1 = in no class --, result()
+    gives den (n_classes, n, m), float64 on the device, in fftfreq order.  Images are added in the order they are handed over,
+    without atomics: the same sequence of updates gives the same bits."""
+
+    def __init__(self, n_classes, n, m, device, scale=1.0):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("spatial_vae_amd: CtfPower must live on a HIP device (got %s); the MI355X path has no CPU "
+                               "fallback" % device)
+        self.n_classes, self.n, self.m, self.scale, self.device = int(n_classes), int(n), int(m), float(scale), device
+        if self.n_classes < 1 or self.n < 2 or self.m < 2:
+            raise RuntimeError("CtfPower: bad n_classes = %d, n = %d or m = %d" % (self.n_classes, self.n, self.m))
+        self.den = torch.zeros(self.n_classes, self.n, self.m, dtype=torch.float64, device=device)
+
+    def update(self, table, label):
+        _require_hip(label, "label")
+        if label.dtype != torch.int32:
+            raise RuntimeError("CtfPower.update: label must be int32")
+        tab = _ctf_rows(table, self.device, "CtfPower.update")
+        B = label.numel()
+        if tab.size(0) != B:
+            raise RuntimeError("CtfPower.update: %d rows of CTF parameters for %d labels" % (tab.size(0), B))
+        _call("svae_ctf_power_update", self.device, tab, label.contiguous(), B, self.n, self.m, self.scale, self.n_classes, self.den)
+
+    def result(self):
+        return self.den
+
+
+def wiener_finish(sum, den, lam, n, m):
+    """The Wiener class averages Re IDFT( DFT(sum[k]) / (den[k] + lam) ) (svae_wiener_finish): sum (n_classes, n*m[, 1]) float64
+    on the device, the real-space sums of aligned CTF-multiplied images (ClassSums.result()[0] at C == 1), den (n_classes, n, m)
+    from CtfPower.  Returns (n_classes, n, m) float32."""
+    _require_hip(sum, "sum")
+    _require_hip(den, "den")
+    n_classes = den.size(0) if den.dim() == 3 else den.numel() // (n * m)
+    if sum.dtype != torch.float64 or den.dtype != torch.float64:
+        raise RuntimeError("wiener_finish: sum and den must be float64")
+    if sum.numel() != n_classes * n * m or den.numel() != n_classes * n * m:
+        raise RuntimeError("wiener_finish: sum %s / den %s do not hold %d one-channel planes of %dx%d"
+                           % (tuple(sum.shape), tuple(den.shape), n_classes, n, m))
+    out = torch.empty(n_classes, n, m, dtype=torch.float32, device=sum.device)
+    ws_bytes = _lib.lib().svae_wiener_finish_workspace_bytes(n_classes, n, m)
+    ws = _buf(sum.device, ws_bytes, "ctfcorr") if ws_bytes else None
+    _call("svae_wiener_finish", sum.device, sum.contiguous(), den.contiguous(), float(lam), n_classes, n, m, out, ws, ws_bytes)
+    return out
 
 
 def ctf_filter(table, n, m, scale=1.0, device=None):

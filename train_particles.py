@@ -80,11 +80,13 @@ def build(args, device):
             return (a - flat.mean(1)[:, None, None]) / flat.std(1)[:, None, None]
         tr, te = norm(tr), norm(te)
     kn, km = (n - 1 if n % 2 == 0 else n), (m - 1 if m % 2 == 0 else m)   # train_particles.py:352-358
-    ctf_train = ctf_test = None
+    ctf_train = ctf_test = ctf_params_train = ctf_params_test = None
     if args.ctf_train is not None:
-        ctf_train = ops.ctf_filter(C.ctf_table(C.parse_ctf(args.ctf_train)), kn, km, scale=args.scale, device=device).unsqueeze(1)
+        ctf_params_train = C.ctf_table(C.parse_ctf(args.ctf_train))
+        ctf_train = ops.ctf_filter(ctf_params_train, kn, km, scale=args.scale, device=device).unsqueeze(1)
     if args.ctf_test is not None:
-        ctf_test = ops.ctf_filter(C.ctf_table(C.parse_ctf(args.ctf_test)), kn, km, scale=args.scale, device=device).unsqueeze(1)
+        ctf_params_test = C.ctf_table(C.parse_ctf(args.ctf_test))
+        ctf_test = ops.ctf_filter(ctf_params_test, kn, km, scale=args.scale, device=device).unsqueeze(1)
     y_train = torch.from_numpy(np.ascontiguousarray(tr)).float().view(-1, n * m)
     y_test = torch.from_numpy(np.ascontiguousarray(te)).float().view(-1, n * m)
     mask = None
@@ -109,7 +111,10 @@ def build(args, device):
                                         bilinear=args.bilinear)
     q_net = models.InferenceNetwork(n * m, inf_dim, args.q_hidden_dim, num_layers=args.q_num_layers, activation=act,
                                     resid=args.resid)
-    return dict(y_train=y_train, y_test=y_test, ctf_train=ctf_train, ctf_test=ctf_test, mask=mask, n=n, m=m, p_net=p_net,
+    # ctf_params_*: the (P, 8) float64 tables the filters were built from, ctf_scale their pixel-size factor (infer.py's
+    # --ctf_correct evaluates the transfer functions on the image's own frequency grid from them)
+    return dict(y_train=y_train, y_test=y_test, ctf_train=ctf_train, ctf_test=ctf_test, ctf_params_train=ctf_params_train,
+                ctf_params_test=ctf_params_test, ctf_scale=float(args.scale), mask=mask, n=n, m=m, p_net=p_net,
                 q_net=q_net, rotate=rotate, translate=translate, augment=args.augment_rotation,
                 table=["Epoch", "Split", "ELBO", "Error", "KL"])
 
