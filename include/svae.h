@@ -20,6 +20,23 @@
  *     in between, as must the parameters, z and the pose themselves; `ws` (svae_workspace_bytes) is
  *     scratch, free to reuse after the call's work has completed on the stream.  Both must be
  *     256-byte aligned.
+ *
+ * Under stream capture (hipStreamBeginCapture on `stream`, or torch.cuda.graph)
+ *   Every entry point that takes a stream may be captured into a HIP graph: a call records its launches and memset nodes on
+ *   the capture stream and executes nothing.  What a replay repeats is exactly those nodes, with the addresses and the host
+ *   numbers of the captured call; nothing the host did at enqueue time happens again:
+ *   - "stateless" is about the device.  The host keeps three tables, all updated at enqueue time and never by a replay: the
+ *     plan record per `saved` address (what svae_decoder_backward checks its `saved` against), the chunk count per
+ *     svae_iw_stream state address (what lets _update / _finish refuse a mismatch), and the svae_path_counts counters.  A
+ *     captured forward + backward pair, or reset + update + finish sequence, is checked once, when it is captured, and
+ *     replays as a whole; a replay counts no paths.
+ *   - host numbers are constants of the graph.  svae_adam_step's `step` (and the bias corrections formed from it) is one: a
+ *     replay applies the captured step's corrections again.  The pair svae_grad_guard_norm + svae_adam_step_guarded is the
+ *     form whose count lives on the device (svae_guard_control.t, step_size, sqrt_bc2) and advances with every replay.
+ *   - run each call once outside a capture first: kernels that need more than the default dynamic LDS have their attribute
+ *     set at enqueue time.
+ *   - svae_profile_enable must be off (see below): its events are not for a capturing stream.
+ *   tests/test_gpu_graph.py replays every entry point against its eager result, bit for bit.
  */
 #ifndef SVAE_H
 #define SVAE_H

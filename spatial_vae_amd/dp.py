@@ -700,15 +700,27 @@ class TrainStep(object):
 
     # ---- optional: the whole step as one HIP graph (single-GPU, fixed shapes) ------------------------
     def capture(self, x, *batch, warmup=3, **kw):
-        """(Needs TrainStep(..., fused_adam=True): torch's capturable Adam keeps its step counter on the device.)
-        Record forward + backward + Adam for inputs of these shapes into a HIP graph (torch.cuda.CUDAGraph:
+        """Record forward + backward + Adam for inputs of these shapes into a HIP graph (torch.cuda.CUDAGraph:
         the C-ABI launches go to the capture stream like any torch op).  Afterwards __call__ copies the batch
         into the static input buffers and replays: ~60 kernel launches become one.  Noise is drawn inside the
-        graph from torch's graph-safe Philox generator, as the reference draws it on the device."""
+        graph from torch's graph-safe Philox generator, as the reference draws it on the device.
+
+        Needs TrainStep(..., fused_adam=True) on a HIP device, single-rank and unguarded: torch's capturable Adam keeps its
+        step counter on the device, where a replay advances it.  ops.FlatAdam hands svae_adam_step the step number and both
+        bias corrections as host numbers, which a graph would freeze at their values of the capture; anything else raises."""
+        if self.device.type != "cuda":
+            raise RuntimeError("TrainStep.capture: a HIP graph needs the step on a HIP device (this one holds its parameters on "
+                               "%s); build it there with fused_adam=True" % (self.device,))
         if world_size() > 1:
-            raise RuntimeError("graph capture is wired for the single-GPU step only")
+            raise RuntimeError("TrainStep.capture: graph capture is wired for the single-GPU step only (fused_adam=True, one rank)")
         if self.guarded:
-            raise RuntimeError("graph capture of the guarded step (clip_grad_norm / skip_nonfinite) is not supported")
+            raise RuntimeError("TrainStep.capture: the guarded step (clip_grad_norm / skip_nonfinite) is not captured; build the "
+                               "step with fused_adam=True and without the guard")
+        group = self.optim.param_groups[0]
+        if not (isinstance(self.optim, torch.optim.Adam) and group.get("capturable")):
+            raise RuntimeError("TrainStep.capture: needs TrainStep(..., fused_adam=True): %s keeps Adam's step count on the host, "
+                               "so a replayed graph would apply the bias corrections of the captured step forever"
+                               % type(self.optim).__name__)
         self._static_x = x
         self._static_batch = [b.clone() if torch.is_tensor(b) else b for b in batch]
         self._static_kw = dict(kw)
@@ -728,6 +740,12 @@ class TrainStep(object):
         kw = {k: v for k, v in kw.items() if k != "global_batch"}
         if weight != 1.0 or kw:
             raise RuntimeError("a captured step replays fixed arguments")
+        if len(batch) != len(self._static_batch):
+            raise RuntimeError("a captured step replays %d batch tensors, got %d" % (len(self._static_batch), len(batch)))
+        for dst, src in zip(self._static_batch, batch):
+            if torch.is_tensor(dst) and (not torch.is_tensor(src) or src.shape != dst.shape):
+                raise RuntimeError("a captured step replays batches of shape %s, got %s"
+                                   % (tuple(dst.shape), tuple(src.shape) if torch.is_tensor(src) else type(src).__name__))
         for dst, src in zip(self._static_batch, batch):
             if torch.is_tensor(dst) and src is not dst:
                 dst.copy_(src, non_blocking=True)

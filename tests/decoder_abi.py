@@ -114,12 +114,13 @@ PER_IMAGE = ("dz",) + POSE_SINKS
 # inputs and references
 # ---------------------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def inputs(name):
-    """float32 numpy inputs of a case, seeded by its name: parameters as nn.Linear / nn.Bilinear draw them
+def inputs(name, seed=0):
+    """float32 numpy inputs of a case, seeded by its name (and `seed`: 0 is the set every reference here is computed on, another
+    value draws a second set of the same shapes): parameters as nn.Linear / nn.Bilinear draw them
     (uniform(+-1/sqrt(fan_in))), z ~ normal, theta ~ uniform(-3, 3), dx ~ 0.1 normal, coordinates uniform(-1, 1),
     dy ~ normal / N, Bernoulli targets k / 255."""
     c = case(name)
-    rs = np.random.RandomState(zlib.crc32(c["name"].encode()) & 0x7FFFFFFF)
+    rs = np.random.RandomState((zlib.crc32(c["name"].encode()) + 7919 * int(seed)) & 0x7FFFFFFF)
     N, B, H, L, C, Zd, ind = (c[k] for k in ("N", "B", "H", "L", "C", "Zd", "in_dim"))
 
     def uni(fan_in, *shape):
@@ -295,13 +296,15 @@ class Forward(object):
     "dll" or "nodll" (svae_decoder_forward_bce with / without dll_dy).  After the call: out (numpy, by name), paths
     (svae_path_counts of this call), bad_guards (names of buffers whose guard bytes changed)."""
 
-    def __init__(self, name, saved=True, logits=True, fill=0x00, bce=None):
+    def __init__(self, name, saved=True, logits=True, fill=0x00, bce=None, seed=0, run=True):
+        """Allocates every buffer of the call; run=False stops there (enqueue() and collect() are then the caller's)."""
         from spatial_vae_amd import _lib
         self._lib, self.L = _lib, _lib.lib()
         self.c = c = case(name)
         self.dev = dev = _dev()
         self.fill = fill
-        p, d = inputs(c["name"])
+        self.bce = bce
+        p, d = inputs(c["name"], seed)
         self.tens = {k: torch.from_numpy(v).to(dev) for k, v in list(p.items()) + list(d.items())}
         self.desc = make_desc(c)
         self.saved_bytes = self.L.svae_saved_bytes(ctypes.byref(self.desc))
@@ -321,23 +324,33 @@ class Forward(object):
             self.bufs["loglik"] = self._out("loglik")
             if bce == "dll":
                 self.bufs["dll_dy"] = self._out("dll_dy")
-        ptr = {k: (self.bufs[k].ptr if k in self.bufs else None) for k in ("y", "logits", "loglik", "dll_dy")}
-        sv = self.saved.ptr if saved else None
+        self.bwd = None
+        if not run:
+            return
         _lib.path_counts(reset=True)
         with torch.cuda.device(dev):
-            if bce:
-                self.rc = self.L.svae_decoder_forward_bce(ctypes.byref(self.desc), ctypes.byref(self.params),
-                                                          ctypes.byref(self.pose), self.z, self.tens["target"].data_ptr(),
-                                                          ptr["y"], ptr["logits"], ptr["loglik"], ptr["dll_dy"], sv, self.ws.ptr,
-                                                          self.ws_bytes, _stream())
-            else:
-                self.rc = self.L.svae_decoder_forward(ctypes.byref(self.desc), ctypes.byref(self.params), ctypes.byref(self.pose),
-                                                      self.z, ptr["y"], ptr["logits"], sv, self.ws.ptr, self.ws_bytes, _stream())
+            self.rc = self.enqueue(_stream())
         _lib.check(self.rc)
         torch.cuda.synchronize()
         self.paths = {k: v for k, v in _lib.path_counts(reset=True).items() if v}
-        self.out, self.bad_guards = _collect(c, self.bufs)
+        self.collect()
+
+    def enqueue(self, stream):
+        """The one svae_decoder_forward[_bce] call on `stream`; returns its status.  Nothing else: no allocation, copy or wait."""
+        ptr = {k: (self.bufs[k].ptr if k in self.bufs else None) for k in ("y", "logits", "loglik", "dll_dy")}
+        sv = self.saved.ptr if self.saved is not None else None
+        if self.bce:
+            return self.L.svae_decoder_forward_bce(ctypes.byref(self.desc), ctypes.byref(self.params), ctypes.byref(self.pose),
+                                                   self.z, self.tens["target"].data_ptr(), ptr["y"], ptr["logits"], ptr["loglik"],
+                                                   ptr["dll_dy"], sv, self.ws.ptr, self.ws_bytes, stream)
+        return self.L.svae_decoder_forward(ctypes.byref(self.desc), ctypes.byref(self.params), ctypes.byref(self.pose), self.z,
+                                           ptr["y"], ptr["logits"], sv, self.ws.ptr, self.ws_bytes, stream)
+
+    def collect(self):
+        """Read the forward's outputs back: out (numpy, by name) and bad_guards."""
+        self.out, self.bad_guards = _collect(self.c, self.bufs)
         self.bad_guards += _guards_only(dict(ws=self.ws, saved=self.saved))
+        return self.out, self.bad_guards
 
     def _out(self, name):
         return Guarded(4 * int(np.prod(_shape(self.c, name))), self.dev).fill_float(SENTINEL)
@@ -360,6 +373,20 @@ class Forward(object):
         NULL, and with no pose sink at all `pg` itself is NULL when null_pg (else a struct of NULLs).  separate_ws: the
         forward's workspace is first overwritten with the fill byte and the call gets a fresh workspace, filled likewise.
         Returns (outputs by name, path counts of this call, names of buffers whose guards changed)."""
+        _lib = self._lib
+        self.alloc_backward(sinks=sinks, dy_scale=dy_scale, separate_ws=separate_ws, null_pg=null_pg)
+        _lib.path_counts(reset=True)
+        with torch.cuda.device(self.dev):
+            rc = self.enqueue_backward(_stream())
+        if check:
+            _lib.check(rc)
+        torch.cuda.synchronize()
+        paths = {k: v for k, v in _lib.path_counts(reset=True).items() if v}
+        out, bad = self.collect_backward()
+        return out, paths, bad
+
+    def alloc_backward(self, sinks=None, dy_scale=None, separate_ws=False, null_pg=False):
+        """Every buffer and struct of the backward call (see backward); kept in self.bwd."""
         _lib, c, dev = self._lib, self.c, self.dev
         sinks = list(sink_names(c) if sinks is None else sinks)
         assert set(sinks) <= set(sink_names(c)), sinks
@@ -378,22 +405,25 @@ class Forward(object):
         if dy_scale is not None:
             scale = torch.from_numpy(np.asarray(dy_scale, np.float32)).to(dev)
             assert scale.shape == (c["B"],)
-        _lib.path_counts(reset=True)
-        with torch.cuda.device(dev):
-            rc = self.L.svae_decoder_backward(ctypes.byref(self.desc), ctypes.byref(self.params), ctypes.byref(self.pose), self.z,
-                                              self.bufs["logits"].ptr, self.tens["dy"].data_ptr(),
-                                              None if scale is None else scale.data_ptr(), self.saved.ptr, ctypes.byref(grads),
-                                              bufs["dz"].ptr if "dz" in bufs else None,
-                                              None if (null_pg and not has_pose) else ctypes.byref(pg), ws.ptr, self.ws_bytes,
-                                              _stream())
-        if check:
-            _lib.check(rc)
-        torch.cuda.synchronize()
-        paths = {k: v for k, v in _lib.path_counts(reset=True).items() if v}
-        out, bad = _collect(c, bufs)
-        bad += _guards_only(dict(ws_backward=ws, ws_forward=self.ws, saved=self.saved, logits=self.bufs["logits"],
+        self.bwd = dict(bufs=bufs, grads=grads, pg=pg, pg_null=null_pg and not has_pose, ws=ws, scale=scale)
+        return self.bwd
+
+    def enqueue_backward(self, stream):
+        """The one svae_decoder_backward call on `stream`; returns its status.  Nothing else."""
+        w = self.bwd
+        bufs = w["bufs"]
+        return self.L.svae_decoder_backward(ctypes.byref(self.desc), ctypes.byref(self.params), ctypes.byref(self.pose), self.z,
+                                            self.bufs["logits"].ptr, self.tens["dy"].data_ptr(),
+                                            None if w["scale"] is None else w["scale"].data_ptr(), self.saved.ptr,
+                                            ctypes.byref(w["grads"]), bufs["dz"].ptr if "dz" in bufs else None,
+                                            None if w["pg_null"] else ctypes.byref(w["pg"]), w["ws"].ptr, self.ws_bytes, stream)
+
+    def collect_backward(self):
+        """(outputs by name, names of buffers whose guards changed) of the backward call."""
+        out, bad = _collect(self.c, self.bwd["bufs"])
+        bad += _guards_only(dict(ws_backward=self.bwd["ws"], ws_forward=self.ws, saved=self.saved, logits=self.bufs["logits"],
                                  y=self.bufs["y"]))
-        return out, paths, bad
+        return out, bad
 
 
 def _collect(c, bufs):

@@ -1,0 +1,87 @@
+"""tests/stream_cases.py without a GPU: the table covers every entry point that takes a stream, its two input sets are what
+the GPU tests assume, and dp.TrainStep.capture refuses a step it cannot capture before it touches torch.cuda."""
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+import stream_cases as S
+from spatial_vae_amd import _lib
+
+
+def test_the_table_covers_exactly_the_entry_points_that_take_a_stream():
+    """The names are derived from the binding's four signature tables (status returned, last argument a bare address), never
+    typed: a new export that takes a stream fails here until it has a case."""
+    derived = S.stream_entry_points()
+    assert len(derived) >= 28 and "svae_decoder_backward" in derived and "svae_wiener_finish" in derived
+    assert "svae_profile_read" not in derived and "svae_saved_bytes" not in derived
+    assert S.covered_entry_points() == derived
+    tables = {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES, **_lib.CTFCORR_SIGNATURES}
+    assert set(derived) <= set(tables)
+    assert len(set(S.NAMES)) == len(S.NAMES)
+
+
+def test_not_capturable_is_small_and_spares_what_the_training_step_needs():
+    assert len(S.NOT_CAPTURABLE) <= 3 and set(S.NOT_CAPTURABLE) <= set(S.stream_entry_points())
+    needed = ("decoder", "loglik", "latent", "head", "linear", "colsum", "adam", "guard")
+    assert not [n for n in S.NOT_CAPTURABLE if any(w in n for w in needed)]
+
+
+@pytest.mark.parametrize("name", S.NAMES)
+def test_both_input_sets_have_one_layout_and_different_values(name):
+    case = S.make_case(name)
+    a, b = case.inputs(0), case.inputs(1)
+    assert list(a) == list(b) and a
+    for k in a:
+        assert a[k].shape == b[k].shape and a[k].dtype == b[k].dtype, k
+        assert a[k].dtype in (np.float32, np.float64, np.int32, np.int64, np.uint8), (k, a[k].dtype)
+        if a[k].dtype.kind == "f" and k != "grad":          # the guard's set B holds one inf on purpose
+            assert np.isfinite(a[k]).all() and np.isfinite(b[k]).all(), k
+        assert not np.array_equal(a[k], b[k]), "%s: %s is the same in both sets" % (name, k)
+    again = case.inputs(0)
+    assert all(np.array_equal(a[k], again[k]) for k in a)
+    assert set(case.state) <= set(a)
+
+
+def test_integer_inputs_are_valid_in_both_sets():
+    for seed in (0, 1):
+        for case in S.make_cases():
+            i = case.inputs(seed)
+            if "quarter" in i:
+                assert set(i["quarter"].tolist()) <= {-1, 0, 1, 2, 3} and (i["quarter"] >= 0).sum() == 4
+            if "label" in i:
+                assert (i["label"] >= -1).all() and (i["label"] < case.n_classes).all()
+            if "mask" in i:
+                assert set(i["mask"].tolist()) <= {0, 1} and i["mask"].any()
+    g = S.Guard()
+    assert np.isfinite(g.inputs(0)["grad"]).all() and np.isinf(g.inputs(1)["grad"]).sum() == 1
+    assert np.isfinite(g.inputs(1, finite=True)["grad"]).all()
+    assert S.Guard.record(g.inputs(1)["control"]).t == 7 and S.Guard.record(g.inputs(0)["control"]).steps == 0
+
+
+def test_the_ctf_cases_take_the_forms_their_names_say():
+    import ref64
+    assert ref64.ctf_form(*S.CTF_LDS_PAIR) == "lds" and S.CTF_LDS_PAIR in ref64.CTF_BOTH_FORMS
+    assert ref64.ctf_form(*S.CTF_GLOBAL_PAIR) == "global" and S.CTF_GLOBAL_PAIR in ref64.CTF_PAIRS
+
+
+def test_capture_on_a_cpu_step_names_the_hip_device():
+    """A CPU step has no stream to capture: a RuntimeError that says so and names fused_adam=True, not an AttributeError or
+    an assertion from torch.cuda.Stream."""
+    from spatial_vae_amd import dp
+
+    def toy(x, y, p_net, q_net, noise=None):
+        z = q_net(y)
+        rec = p_net(z[:, :2] + noise)
+        elbo = -((rec - y) ** 2).sum(1).mean() - (z ** 2).mean()
+        return elbo, elbo.detach(), elbo.detach()
+
+    torch.manual_seed(1)
+    step = dp.TrainStep(nn.Sequential(nn.Linear(2, 8), nn.Tanh(), nn.Linear(8, 5)),
+                        nn.Sequential(nn.Linear(5, 8), nn.Tanh(), nn.Linear(8, 4)), toy, lr=1e-2)
+    y, noise = torch.randn(6, 5), torch.randn(6, 2)
+    with pytest.raises(RuntimeError, match="HIP device") as info:
+        step.capture(None, y, noise=noise)
+    assert "fused_adam=True" in str(info.value) and "cpu" in str(info.value)
+    assert step._graph is None
+    step(None, y, noise=noise)                              # the refused capture left the eager step usable
