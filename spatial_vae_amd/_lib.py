@@ -149,6 +149,21 @@ CTFCORR_SIGNATURES = {
 CTF_MODE = {"flip": 0, "multiply": 1}
 
 
+# ---- include/svae_cluster.h: k-means over the content latents, a fifth header with a table of its own ----
+# Same rules (tests/test_cluster_cpu.py holds these rows, and the mirror of the header's one struct, to that header).  `rec` is
+# the address of a record in device memory, like svae_grad_guard_norm's `control`.  The header adds no constant.
+class KMeansRecord(ctypes.Structure):
+    """svae_kmeans_record: all zero bytes = a fresh record."""
+    _fields_ = [("iterations", i64), ("changed", i64), ("converged_at", i64), ("assigned", i64), ("empty", i64), ("inertia", f64)]
+
+
+CLUSTER_SIGNATURES = {
+    "svae_kmeans_workspace_bytes": (sz, [i64, i32, i32]),
+    "svae_kmeans_seed": (cint, [vp, i64, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "svae_kmeans_step": (cint, [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -171,7 +186,8 @@ def lib():
         raise RuntimeError("spatial_vae_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
-    for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES,
+                                      **CLUSTER_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

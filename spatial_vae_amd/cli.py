@@ -719,6 +719,8 @@ INFER_MAX_CHUNK = 1024      # samples per image in one decoder call (the kernels
 INFER_PATH_OVERRIDES = ("train_path", "test_path", "ctf_train", "ctf_test")
 INFER_MAX_CLASSES = 4096    # classes of --labels (svae_class_sums_update's limit)
 INFER_STACK_FORMATS = (".npy", ".mrcs")
+INFER_MAX_CLUSTERS = min(INFER_MAX_CLASSES, 1024)   # classes of --cluster (include/svae_cluster.h's limit on k)
+INFER_MAX_RESTARTS = 16
 
 
 def infer_arguments(argv=None):
@@ -769,8 +771,42 @@ def infer_arguments(argv=None):
     p.add_argument("--wiener_lambda", type=float, default=None, metavar="X", help="with --ctf_correct wiener: the regulariser, "
                    "X >= 0, the reciprocal of the per-particle spectral signal-to-noise ratio assumed (default 1.0: a convention, not "
                    "a tuned value; the .npz keeps numerator and denominator, so another X needs no second run)")
+    p.add_argument("--cluster", type=int, default=None, metavar="K", help="k-means of the content latents into K classes on the "
+                   "device (2..%d, at most the number of images), seeded by k-means++; the classes take the place of --labels for "
+                   "--class_averages, and --pose selects whose content latents are clustered (z_iw, z_best or z_q)" % INFER_MAX_CLUSTERS)
+    p.add_argument("--cluster_out", metavar="PATH.npz", help="with --cluster (required): labels, centres, members, inertia, the "
+                   "seeds, every restart's inertia and the decoder's un-posed reconstruction of each centre")
+    p.add_argument("--cluster_labels", metavar="PATH.npy", help="with --cluster: also write the labels in the format --labels reads")
+    p.add_argument("--cluster_iters", type=int, default=None, metavar="I", help="Lloyd iterations per restart, I >= 1 (default 100; "
+                   "iterations after convergence change nothing)")
+    p.add_argument("--cluster_restarts", type=int, default=None, metavar="R", help="independent seedings, 1..%d (default 1); the one "
+                   "of lowest inertia is kept, the first of equals" % INFER_MAX_RESTARTS)
+    p.add_argument("--cluster_seed", type=int, default=None, metavar="S", help="seed of the generator the k-means++ uniforms come "
+                   "from (default --seed)")
     args = p.parse_args(argv)
     args.train_argv = train_argv
+    if args.cluster is None:
+        for name in ("cluster_out", "cluster_labels", "cluster_iters", "cluster_restarts", "cluster_seed"):
+            if getattr(args, name) is not None:
+                p.error("--%s needs --cluster" % name)
+    else:
+        if not 2 <= args.cluster <= INFER_MAX_CLUSTERS:
+            p.error("--cluster must be in [2, %d] (got %d)" % (INFER_MAX_CLUSTERS, args.cluster))
+        if args.labels is not None:
+            p.error("--cluster makes the classes itself: it excludes --labels")
+        if args.cluster_out is None:
+            p.error("--cluster needs --cluster_out")
+        if os.path.splitext(args.cluster_out)[1] != ".npz":
+            p.error("--cluster_out must end in .npz (got %s)" % args.cluster_out)
+        if args.cluster_labels is not None and os.path.splitext(args.cluster_labels)[1] != ".npy":
+            p.error("--cluster_labels must end in .npy (got %s)" % args.cluster_labels)
+        args.cluster_iters = 100 if args.cluster_iters is None else args.cluster_iters
+        args.cluster_restarts = 1 if args.cluster_restarts is None else args.cluster_restarts
+        args.cluster_seed = args.seed if args.cluster_seed is None else args.cluster_seed
+        if args.cluster_iters < 1:
+            p.error("--cluster_iters must be >= 1")
+        if not 1 <= args.cluster_restarts <= INFER_MAX_RESTARTS:
+            p.error("--cluster_restarts must be in [1, %d]" % INFER_MAX_RESTARTS)
     if args.ctf_correct is not None and args.script != "particles":
         p.error("--ctf_correct is for particles (the script whose images have a CTF), not %s" % args.script)
     if args.ctf_correct == "flip" and args.aligned is None and args.class_averages is None:
@@ -812,7 +848,7 @@ def infer_arguments(argv=None):
         p.error("--labels needs --class_averages")
     if args.aligned is None and args.recon is None and args.class_averages is None:
         for name in ("pose", "interp"):
-            if getattr(args, name) is not None:
+            if getattr(args, name) is not None and not (name == "pose" and args.cluster is not None):
                 p.error("--%s needs one of --aligned, --recon, --class_averages" % name)
     args.pose, args.interp = args.pose or "iw", args.interp or "bicubic"
     args.label_array = None
@@ -975,6 +1011,15 @@ def infer_main(args, parser_fn, build, positional=()):
     images, n, m = data.size(0), cfg["n"], cfg["m"]
     channels = data[0].numel() // (n * m) if images else 1
     labels = getattr(args, "label_array", None)
+    cluster = getattr(args, "cluster", None)        # --cluster K: the classes come from k-means of the content latents
+    if cluster is not None:
+        z_dim = inf_dim - (1 if rotate else 0) - (2 if translate else 0)
+        if z_dim < 1:
+            _refuse("--cluster groups the content latents, and this model has none (z_dim = 0)")
+        if z_scale == 0:
+            _refuse("--cluster: this state is from before the run's z_delay ended (z_scale = 0): every content latent is 0")
+        if cluster > images:
+            _refuse("--cluster {} exceeds the {} images of the {} split".format(cluster, images, args.split))
     if labels is not None and labels.shape[0] != images:
         _refuse("--labels has {} entries, the {} split has {} images".format(labels.shape[0], args.split, images))
     for k in ("aligned", "recon"):
@@ -983,12 +1028,16 @@ def infer_main(args, parser_fn, build, positional=()):
     stacks = {k: torch.empty(images, n * m * channels, dtype=torch.float32, pin_memory=True)      # filled by non-blocking copies
               for k in ("aligned", "recon") if want[k] is not None}
     sums = None
+    label_d = None
     if want["class_averages"] is not None:
-        if labels is None:
-            labels = np.zeros(images, np.int64)     # one class holding every image
-        n_classes = max(int(labels.max()) + 1, 1) if images else 1
+        if cluster is not None:
+            n_classes = cluster                     # the labels arrive on the device, after the scoring pass
+        else:
+            if labels is None:
+                labels = np.zeros(images, np.int64)     # one class holding every image
+            n_classes = max(int(labels.max()) + 1, 1) if images else 1
+            label_d = torch.from_numpy(labels.astype(np.int32)).to(device)
         sums = ops.ClassSums(n_classes, n * m, channels, device)
-        label_d = torch.from_numpy(labels.astype(np.int32)).to(device)
     # --ctf_correct: each image through its own transfer function (the table rows of the split, uploaded once) before it is aligned
     correct = getattr(args, "ctf_correct", None)
     table_d = wiener = None
@@ -1010,6 +1059,22 @@ def infer_main(args, parser_fn, build, positional=()):
     gen = torch.Generator()
     gen.manual_seed(args.seed)
     rows = []
+
+    def align_and_update(lo, y, per_image, q_mu, labelled):
+        """One minibatch brought into the canonical frame; with `labelled` also its class-sum and Wiener updates under label_d.
+        The scoring walk and --cluster's second walk both make exactly these calls, in this order."""
+        seen = y if correct != "flip" else ops.ctf_apply(y, table_d[lo:lo + bs], n, m, ctf_scale, "flip")
+        aligned, cover = E.align_minibatch(seen, n, m, per_image, q_mu, rotate, translate, args.pose, args.interp)
+        if labelled and wiener is not None:
+            g = ops.ctf_apply(y, table_d[lo:lo + bs], n, m, ctf_scale, "multiply")
+            g, g_cover = E.align_minibatch(g, n, m, per_image, q_mu, rotate, translate, args.pose, args.interp)
+            wiener[0].update(g, g_cover, label_d[lo:lo + bs])
+            wiener[1].update(table_d[lo:lo + bs], label_d[lo:lo + bs])
+        if labelled:
+            sums.update(aligned, cover, label_d[lo:lo + bs])
+        return aligned
+
+    labelled = sums is not None and cluster is None     # --cluster: the labels do not exist yet, the updates wait for them
     for lo in range(0, images, bs):                 # dataset order, nothing read back inside the loop
         y = data[lo:lo + bs]
         noise = torch.empty(y.size(0) * K, inf_dim).normal_(generator=gen).to(device, non_blocking=True)
@@ -1017,26 +1082,32 @@ def infer_main(args, parser_fn, build, positional=()):
                                 translate=translate, dx_scale=targs.dx_scale, theta_prior=targs.theta_prior, z_scale=z_scale,
                                 mask=mask, ctf=None if ctf is None else ctf[lo:lo + bs], noise=noise)
         rows.append(torch.cat([out["per_image"], out["q_mu"], out["q_std"]], 1))
-        if "aligned" in stacks or sums is not None:
-            seen = y if correct != "flip" else ops.ctf_apply(y, table_d[lo:lo + bs], n, m, ctf_scale, "flip")
-            aligned, cover = E.align_minibatch(seen, n, m, out["per_image"], out["q_mu"], rotate, translate, args.pose, args.interp)
-            if wiener is not None:
-                g = ops.ctf_apply(y, table_d[lo:lo + bs], n, m, ctf_scale, "multiply")
-                g, g_cover = E.align_minibatch(g, n, m, out["per_image"], out["q_mu"], rotate, translate, args.pose, args.interp)
-                wiener[0].update(g, g_cover, label_d[lo:lo + bs])
-                wiener[1].update(table_d[lo:lo + bs], label_d[lo:lo + bs])
-            if sums is not None:
-                sums.update(aligned, cover, label_d[lo:lo + bs])
+        if "aligned" in stacks or labelled:
+            aligned = align_and_update(lo, y, out["per_image"], out["q_mu"], labelled)
             if "aligned" in stacks:
                 stacks["aligned"][lo:lo + bs].copy_(aligned.view(y.size(0), -1), non_blocking=True)
         if "recon" in stacks:
             zc = E.content_latents(out["per_image"], out["q_mu"], rotate, translate, args.pose)
             recon = E.reconstruct_unposed(x, p_net, y.size(0), zc, gaussian_mean=(script == "particles"))
             stacks["recon"][lo:lo + bs].copy_(recon.reshape(y.size(0), -1), non_blocking=True)
+    width = 6 + 2 * inf_dim
+    fit = None
+    if cluster is not None:
+        # k-means of every image's content latents, then (for --class_averages) a second walk over the minibatches that re-aligns
+        # from the stored rows and makes the update calls the scoring pass would have made, in its order; no host read in between
+        all_rows = torch.cat(rows)
+        zc = E.content_latents(all_rows[:, :width], all_rows[:, width:width + inf_dim], rotate, translate, args.pose)
+        kgen = torch.Generator()
+        kgen.manual_seed(args.cluster_seed)
+        fit = E.cluster_latents(zc, cluster, args.cluster_iters, args.cluster_restarts, kgen)
+        label_d = fit["label"]
+        if sums is not None:
+            for i, lo in enumerate(range(0, images, bs)):
+                align_and_update(lo, data[lo:lo + bs], rows[i][:, :width], rows[i][:, width:width + inf_dim], True)
+        centre_recon = E.reconstruct_unposed(x, p_net, cluster, fit["centres"].float(), gaussian_mean=(script == "particles"))
     host = torch.cat(rows).cpu().numpy()            # the one transfer of the scores
     if stacks:
         torch.cuda.synchronize(device)              # the one synchronisation: every minibatch's copy has landed
-    width = 6 + 2 * inf_dim
     arrays = score_arrays(host[:, :width], host[:, width:width + inf_dim], host[:, width + inf_dim:], rotate, translate)
     means = [float(np.mean(arrays[k], dtype=np.float64)) for k in ("bound", "loglik", "kl")]
     meta = {"script": script, "state": args.state, "generator": args.generator, "inference": args.inference, "num_samples": K,
@@ -1046,6 +1117,16 @@ def infer_main(args, parser_fn, build, positional=()):
         meta.update(pose=args.pose, interp=args.interp, labels=args.labels, **want)
     if correct is not None:
         meta.update(ctf_correct=correct, wiener_lambda=args.wiener_lambda)
+    if cluster is not None:
+        meta.update(pose=args.pose, cluster=cluster, cluster_out=args.cluster_out, cluster_labels=args.cluster_labels,
+                    cluster_iters=args.cluster_iters, cluster_restarts=args.cluster_restarts, cluster_seed=args.cluster_seed)
+        labels = fit["label"].cpu().numpy().astype(np.int64)
+        record = ops.KMeans.read_record(fit["record"])
+        found = {"label": labels, "centres": fit["centres"].cpu().numpy(), "members": fit["members"].cpu().numpy(),
+                 "inertia": np.float64(record["inertia"]), "iterations": np.int64(record["iterations"]),
+                 "converged_at": np.int64(record["converged_at"]), "seed_index": fit["seed_index"].cpu().numpy().astype(np.int64),
+                 "restart_inertia": fit["restart_inertia"].cpu().numpy(), "chosen_restart": np.int64(fit["chosen_restart"].item()),
+                 "centre_recon": centre_recon.cpu().numpy().reshape(cluster, n, m, -1), "meta": np.array(json.dumps(meta))}
     arrays["meta"] = np.array(json.dumps(meta))
     for k, stack in stacks.items():
         write_stack(want[k], stack.numpy().reshape(images, n, m, channels))
@@ -1062,6 +1143,10 @@ def infer_main(args, parser_fn, build, positional=()):
                            wiener_average=w_avg.cpu().numpy().reshape(sums.n_classes, n, m, 1),
                            wiener_lambda=np.float64(args.wiener_lambda))
         write_npz(want["class_averages"], classes)
+    if cluster is not None:
+        write_npz(args.cluster_out, found)
+        if args.cluster_labels is not None:
+            write_atomically(args.cluster_labels, lambda f: np.save(f, labels))
     write_npz(args.out, arrays)
     print("images {}\tbound {!r}\tlog p(x|z) {!r}\tKL {!r}\tmedian ESS {:.3f}".format(
         host.shape[0], means[0], means[1], means[2], float(np.median(arrays["ess"]))))

@@ -16,6 +16,7 @@
 #include "../../include/svae_stream.h"
 #include "../../include/svae_align.h"
 #include "../../include/svae_ctfcorr.h"
+#include "../../include/svae_cluster.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
@@ -23,6 +24,7 @@
 #include "iw_stream.h"
 #include "align.h"
 #include "ctfcorr.h"
+#include "cluster.h"
 #include "encoder.h"
 #include "split.h"
 
@@ -1859,6 +1861,78 @@ int svae_wiener_finish(const double* sum, const double* den, double lambda, int3
     if (!sum || !den || !average) return fail(SVAE_E_INVALID, "svae_wiener_finish: null sum, den or average");
     return dft_launch("svae_wiener_finish", wiener_finish_kernel<false>, wiener_finish_kernel<true>, n_classes, n, m, ws,
                       static_cast<hipStream_t>(stream), sum, den, lambda, (int)n_classes, (int)n, (int)m, average);
+}
+
+// ---- k-means over the content latents (include/svae_cluster.h) ----
+namespace {
+// the geometry and workspace rules the two k-means calls share; 0 or the refusal
+int kmeans_check(const char* who, int64_t N, int32_t D, int32_t k, const void* ws, size_t ws_bytes) {
+    if (D < 1 || D > kKmeansMaxD || k < 1 || k > kKmeansMaxK || N < k || N > 0x7fffffffLL)
+        return fail(SVAE_E_INVALID, "%s: bad sizes N=%lld D=%d k=%d (1 <= D <= %d, 1 <= k <= %d, k <= N < 2^31)", who, (long long)N, D, k,
+                    kKmeansMaxD, kKmeansMaxK);
+    if (!ws) return fail(SVAE_E_WORKSPACE, "%s: null workspace", who);
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(SVAE_E_WORKSPACE, "%s: workspace not 256-byte aligned", who);
+    const size_t need = kmeans_ws_words((long)N, D, k) * 8;
+    if (ws_bytes < need) return fail(SVAE_E_WORKSPACE, "%s: workspace too small: %zu < %zu", who, ws_bytes, need);
+    return SVAE_OK;
+}
+inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
+}  // namespace
+
+size_t svae_kmeans_workspace_bytes(int64_t N, int32_t D, int32_t k) {
+    if (D < 1 || D > kKmeansMaxD || k < 1 || k > kKmeansMaxK || N < k || N > 0x7fffffffLL) return 0;
+    return kmeans_ws_words((long)N, D, k) * 8;
+}
+
+int svae_kmeans_seed(const float* x, int64_t N, int32_t D, int32_t k, const double* u, double* centres, int32_t* seed_index,
+                     void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (!x || !u || !centres || !seed_index) return fail(SVAE_E_INVALID, "svae_kmeans_seed: null x, u, centres or seed_index");
+    if (misaligned8(u) || misaligned8(centres)) return fail(SVAE_E_INVALID, "svae_kmeans_seed: u and centres must be 8-byte aligned");
+    if (const int rc = kmeans_check("svae_kmeans_seed", N, D, k, ws, ws_bytes)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long P = kmeans_chunk((long)N);
+    const int chunks = (int)(((long)N + P - 1) / P);
+    const KmeansWs w = kmeans_ws(ws, (long)N, D, k);
+    Scope prof(K_AUGMENT, st);
+    for (int j = 0; j < k; ++j) {
+        if (j > 0) {
+            const int first = j == 1 ? 1 : 0;
+            if (D <= 4)
+                hipLaunchKernelGGL(kmeans_seed_dist_kernel<4>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, P, centres, j - 1, first, w);
+            else if (D <= 16)
+                hipLaunchKernelGGL(kmeans_seed_dist_kernel<16>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, P, centres, j - 1, first, w);
+            else
+                hipLaunchKernelGGL(kmeans_seed_dist_kernel<64>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, P, centres, j - 1, first, w);
+        }
+        hipLaunchKernelGGL(kmeans_seed_pick_kernel, dim3(1), dim3(256), 0, st, x, (long)N, D, P, chunks, j, u, centres, seed_index, w);
+    }
+    return launch_status("svae_kmeans_seed");
+}
+
+int svae_kmeans_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t update, double* centres, int32_t* label,
+                     int64_t* members, svae_kmeans_record* rec, void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (!x || !centres || !label || !members || !rec) return fail(SVAE_E_INVALID, "svae_kmeans_step: null x, centres, label, members or rec");
+    if (misaligned8(centres) || misaligned8(members) || misaligned8(rec))
+        return fail(SVAE_E_INVALID, "svae_kmeans_step: centres, members and rec must be 8-byte aligned");
+    if (const int rc = kmeans_check("svae_kmeans_step", N, D, k, ws, ws_bytes)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long P = kmeans_chunk((long)N);
+    const int chunks = (int)(((long)N + P - 1) / P);
+    const KmeansWs w = kmeans_ws(ws, (long)N, D, k);
+    const int up = update ? 1 : 0;
+    const long long* iterations = reinterpret_cast<const long long*>(&rec->iterations);
+    long long* mem = reinterpret_cast<long long*>(members);
+    Scope prof(K_AUGMENT, st);
+    if (D <= 4)
+        hipLaunchKernelGGL(kmeans_assign_kernel<4>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, centres, label, iterations, w);
+    else if (D <= 16)
+        hipLaunchKernelGGL(kmeans_assign_kernel<16>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, centres, label, iterations, w);
+    else
+        hipLaunchKernelGGL(kmeans_assign_kernel<64>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, centres, label, iterations, w);
+    hipLaunchKernelGGL(kmeans_accumulate_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, up, label, w);
+    hipLaunchKernelGGL(kmeans_tail_kernel, dim3(blocks_for(up ? (long)k * D : (long)k)), dim3(256), 0, st, D, k, chunks, up, centres, mem,
+                       rec, w);
+    return launch_status("svae_kmeans_step");
 }
 
 int svae_gemm_mode_set(int mode) {

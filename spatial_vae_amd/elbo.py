@@ -268,6 +268,28 @@ def content_latents(per_image, q_mu, rotate, translate, pose="iw"):
     return _pose_rows(per_image, q_mu, pose)[:, c0:].contiguous()
 
 
+@torch.no_grad()
+def cluster_latents(points, k, iters, restarts=1, generator=None):
+    """k-means of the content latents `points` (N, D) fp32 on the device into k classes (ops.KMeans: k-means++ seeding, `iters`
+    Lloyd steps, a final labelling), `restarts` times from uniforms drawn (restarts, k) from the HOST generator; the run of
+    lowest inertia is picked on the device (torch.argmin: the first of equals) without synchronising.  Returns device tensors:
+    {"label" (N) int32, -1 = a point with a non-finite coordinate; "centres" (k, D) float64; "members" (k) int64; "record" (the
+    svae_kmeans_record, ops.KMeans.read_record); "seed_index" (k) int32; "restart_inertia" (restarts) float64;
+    "chosen_restart" (1) int64}."""
+    restarts = int(restarts)
+    if restarts < 1:
+        raise RuntimeError("cluster_latents: restarts must be >= 1, got %d" % restarts)
+    points = points.float().contiguous()
+    uniforms = torch.rand(restarts, int(k), dtype=torch.float64, generator=generator)
+    km = ops.KMeans(k, points.size(1), points.device)
+    fits = [km.fit(points, iters, uniforms[r]) for r in range(restarts)]
+    inertia = torch.cat([ops.KMeans.inertia(f.record) for f in fits])
+    chosen = torch.argmin(inertia, 0, keepdim=True)
+    out = {name: torch.stack([getattr(f, name) for f in fits]).index_select(0, chosen)[0] for name in ops.KMeansFit._fields}
+    out.update(restart_inertia=inertia, chosen_restart=chosen)
+    return out
+
+
 def _decode_on_grid(x, p_net, B, zc):
     """The decoder on the un-posed grid at the content latents zc."""
     if hasattr(p_net, "forward_posed"):

@@ -51,7 +51,7 @@ def _p(t):
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
                  for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES,
-                                             **_lib.CTFCORR_SIGNATURES}.items()}
+                                             **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -774,6 +774,69 @@ def wiener_finish(sum, den, lam, n, m):
     ws = _buf(sum.device, ws_bytes, "ctfcorr") if ws_bytes else None
     _call("svae_wiener_finish", sum.device, sum.contiguous(), den.contiguous(), float(lam), n_classes, n, m, out, ws, ws_bytes)
     return out
+
+
+KMeansFit = namedtuple("KMeansFit", "label centres members record seed_index")
+
+
+class KMeans:
+    """k-means of (N, D) fp32 points into k classes on the device (include/svae_cluster.h): k-means++ seeding from host-drawn
+    uniforms, then Lloyd steps.  Every sum has a fixed order and nothing is atomic, so the same points and uniforms give the
+    same bits; nothing is read back.  A point with a non-finite coordinate gets the label -1 and enters nothing."""
+
+    RECORD_WORDS = ctypes.sizeof(_lib.KMeansRecord) // 8
+
+    def __init__(self, k, D, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("spatial_vae_amd: KMeans must live on a HIP device (got %s); the MI355X path has no CPU "
+                               "fallback" % device)
+        self.k, self.D, self.device = int(k), int(D), device
+        if not (1 <= self.k <= 1024 and 1 <= self.D <= 64):
+            raise RuntimeError("KMeans: k = %d must be in 1..1024 and D = %d in 1..64" % (self.k, self.D))
+
+    def fit(self, points, iters, uniforms):
+        """Seed, `iters` update steps and one final assign-only step, all enqueued on the current stream.  points: (N, D) fp32
+        contiguous on the device, N >= k; uniforms: k numbers in [0, 1), a host array or a float64 device tensor.  Returns
+        KMeansFit of device tensors: label (N) int32, centres (k, D) float64, members (k) int64, record (the svae_kmeans_record
+        as 6 int64 words, see read_record; its last word holds the inertia's bits) and seed_index (k) int32."""
+        _require_hip(points, "points")
+        if points.dtype != torch.float32 or points.dim() != 2 or points.size(1) != self.D or not points.is_contiguous():
+            raise RuntimeError("KMeans.fit: points must be a contiguous (N, %d) float32 tensor, got %s %s"
+                               % (self.D, tuple(points.shape), points.dtype))
+        N, iters = points.size(0), int(iters)
+        if N < self.k or iters < 0:
+            raise RuntimeError("KMeans.fit: %d points for k = %d, iters = %d" % (N, self.k, iters))
+        u = uniforms if torch.is_tensor(uniforms) else torch.from_numpy(np.array(uniforms, dtype=np.float64, order="C"))
+        if u.dtype != torch.float64 or u.numel() != self.k:
+            raise RuntimeError("KMeans.fit: uniforms must be %d float64 numbers, got %s %s" % (self.k, tuple(u.shape), u.dtype))
+        u = u.reshape(-1).to(self.device).contiguous()
+        dev, k, D = self.device, self.k, self.D
+        ws_bytes = _lib.lib().svae_kmeans_workspace_bytes(N, D, k)
+        if ws_bytes == 0:
+            raise RuntimeError("KMeans.fit: bad geometry N = %d, D = %d, k = %d" % (N, D, k))
+        ws = _buf(dev, ws_bytes, "kmeans")
+        out = KMeansFit(torch.empty(N, dtype=torch.int32, device=dev), torch.empty(k, D, dtype=torch.float64, device=dev),
+                        torch.empty(k, dtype=torch.int64, device=dev), torch.zeros(self.RECORD_WORDS, dtype=torch.int64, device=dev),
+                        torch.empty(k, dtype=torch.int32, device=dev))
+        _call("svae_kmeans_seed", dev, points, N, D, k, u, out.centres, out.seed_index, ws, ws.numel())
+        for update in [1] * iters + [0]:
+            _call("svae_kmeans_step", dev, points, N, D, k, update, out.centres, out.label, out.members, out.record, ws, ws.numel())
+        return out
+
+    @staticmethod
+    def inertia(record):
+        """The record's inertia as a one-element float64 device tensor (a view: no synchronisation)."""
+        return record[_lib.KMeansRecord.inertia.offset // 8:][:1].view(torch.float64)
+
+    @staticmethod
+    def read_record(record):
+        """{iterations, changed, converged_at, assigned, empty, inertia} of a record tensor: synchronises."""
+        rec = _lib.KMeansRecord()
+        ctypes.memmove(ctypes.byref(rec), record.cpu().numpy().tobytes(), ctypes.sizeof(rec))
+        out = {name: int(getattr(rec, name)) for name, _ in _lib.KMeansRecord._fields_[:-1]}
+        out["inertia"] = float(rec.inertia)
+        return out
 
 
 def ctf_filter(table, n, m, scale=1.0, device=None):
