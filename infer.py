@@ -5,7 +5,7 @@ image in dataset order.  On request also what the poses are for: every image bro
 (--aligned), its pose-free reconstruction (--recon) and the averages of the aligned images, overall or per class of --labels
 (--class_averages); for particles with a CTF table, --ctf_correct flip / wiener corrects each image by its own transfer function
 first.  The reference has no such entry point (its command lines end at the .sav files and the table of
-minibatch means).  The work is in spatial_vae_amd/cli.py (infer_main) and spatial_vae_amd/elbo.py (score_minibatch,
+minibatch means).  The work is in spatial_vae_amd/infer.py (infer_main) and spatial_vae_amd/elbo.py (score_minibatch,
 align_minibatch, reconstruct_unposed).
 
   python infer.py mnist --state outputs_run/trained/run_state_epoch10.ckpt --out scores.npz --num_samples 5000 --chunk 50
@@ -23,11 +23,11 @@ TRAINERS = {"mnist": ("train_mnist", "mnist_arguments", ()),
 
 
 def main(argv=None):
-    from spatial_vae_amd import cli
-    args = cli.infer_arguments(argv)
+    from spatial_vae_amd import infer as pipeline
+    args = pipeline.infer_arguments(argv)
     module, parser, positional = TRAINERS[args.script]
     trainer = importlib.import_module(module)
-    return cli.infer_main(args, getattr(trainer, parser), trainer.build, positional)
+    return pipeline.infer_main(args, getattr(trainer, parser), trainer.build, positional)
 
 
 if __name__ == "__main__":

@@ -712,442 +712,3 @@ def synthetic_images(kind, count, n, m, channels, seed):
     u = rs.uniform(size=shape)
     keep = rs.uniform(size=shape) > (0.8 if channels == 1 else 0.0)
     return np.floor(u * keep * 255.0).astype(np.float32)
-
-
-# ---- infer.py: apply a trained model to a dataset, one row per image --------------------------------------------------------
-INFER_MAX_CHUNK = 1024      # samples per image in one decoder call (the kernels' SVAE_IW_MAX_SAMPLES)
-INFER_PATH_OVERRIDES = ("train_path", "test_path", "ctf_train", "ctf_test")
-INFER_MAX_CLASSES = 4096    # classes of --labels (svae_class_sums_update's limit)
-INFER_STACK_FORMATS = (".npy", ".mrcs")
-INFER_MAX_CLUSTERS = min(INFER_MAX_CLASSES, 1024)   # classes of --cluster (include/svae_cluster.h's limit on k)
-INFER_MAX_RESTARTS = 16
-
-
-def infer_arguments(argv=None):
-    """infer.py's command line.  Everything after a bare `--` is kept aside (args.train_argv): with --generator/--inference
-    it is the training script's own flags, parsed later by that script's parser.  Refusals (exit code 2) are made here, before
-    anything touches a GPU or loads the kernel library."""
-    import argparse
-    argv = list(sys.argv[1:] if argv is None else argv)
-    train_argv = None
-    if "--" in argv:
-        cut = argv.index("--")
-        argv, train_argv = argv[:cut], argv[cut + 1:]
-    p = argparse.ArgumentParser("infer.py", description="Per-image pose, latents and K-sample importance-weighted likelihood "
-                                "of a trained spatial-VAE")
-    p.add_argument("script", choices=sorted(SCRIPTS), help="which training script made the model")
-    p.add_argument("--state", metavar="PATH.ckpt", help="training state file (--checkpoint_interval): model, arguments, dataset")
-    p.add_argument("--generator", metavar="G.sav", help="whole-module generator file; with --inference and, after `--`, the "
-                   "training script's own flags")
-    p.add_argument("--inference", metavar="Q.sav")
-    p.add_argument("--out", required=True, metavar="scores.npz")
-    p.add_argument("--split", choices=["test", "train"], default="test")
-    p.add_argument("--num_samples", type=int, default=64, metavar="K", help="samples per image (any K >= 1; default 64)")
-    p.add_argument("--chunk", type=int, default=64, metavar="C",
-                   help="samples per image decoded at once, 1..%d (default 64): memory is that of a B*C minibatch" % INFER_MAX_CHUNK)
-    p.add_argument("--minibatch_size", type=int, default=100, metavar="B")
-    p.add_argument("--seed", type=int, default=0, help="seed of the generator the N(0,1) draws come from")
-    p.add_argument("-d", "--device", type=int, default=-2)
-    for name in INFER_PATH_OVERRIDES:
-        p.add_argument("--" + name, default=None, help="instead of the path stored in the state file")
-    p.add_argument("--aligned", metavar="PATH", help="also write every image brought into the model's canonical frame (its "
-                   "pose removed), in dataset order: .npy = (images, rows, cols, C) float32, .mrcs = an MRC stack (one channel "
-                   "only).  The observed images resampled, nothing else: not masked, and CTF-corrected only under --ctf_correct flip")
-    p.add_argument("--recon", metavar="PATH", help="also write every image's pose-free reconstruction (the decoder on the "
-                   "un-posed grid at the image's content latents), same formats")
-    p.add_argument("--class_averages", metavar="PATH.npz", help="also write the sums, counts and averages of the aligned images "
-                   "over the pixels each image covers: per class of --labels, else one class of all images")
-    p.add_argument("--labels", metavar="PATH.npy", help="integer class per image of the split, -1 = in no class (with "
-                   "--class_averages; at most %d classes)" % INFER_MAX_CLASSES)
-    p.add_argument("--pose", choices=list(E.POSES), default=None, help="which estimate aligns, and whose content latents --recon "
-                   "decodes: the importance-weighted mean (iw, the default), the best sample, or q's mean")
-    p.add_argument("--interp", choices=["bicubic", "bilinear"], default=None, help="resampling of --aligned / --class_averages "
-                   "(default bicubic: Catmull-Rom)")
-    p.add_argument("--ctf_correct", choices=["flip", "wiener"], default=None, help="particles with a CTF table only: correct each "
-                   "observed image by its own transfer function H before it is aligned.  flip: multiply its Fourier coefficients "
-                   "by the sign of H; --aligned and the class averages then hold phase-flipped particles.  wiener: leave those as "
-                   "they are and add to --class_averages the Wiener averages sum(H y) / (sum(H^2) + lambda) per class, with their "
-                   "numerator and denominator.  Scoring is untouched either way")
-    p.add_argument("--wiener_lambda", type=float, default=None, metavar="X", help="with --ctf_correct wiener: the regulariser, "
-                   "X >= 0, the reciprocal of the per-particle spectral signal-to-noise ratio assumed (default 1.0: a convention, not "
-                   "a tuned value; the .npz keeps numerator and denominator, so another X needs no second run)")
-    p.add_argument("--cluster", type=int, default=None, metavar="K", help="k-means of the content latents into K classes on the "
-                   "device (2..%d, at most the number of images), seeded by k-means++; the classes take the place of --labels for "
-                   "--class_averages, and --pose selects whose content latents are clustered (z_iw, z_best or z_q)" % INFER_MAX_CLUSTERS)
-    p.add_argument("--cluster_out", metavar="PATH.npz", help="with --cluster (required): labels, centres, members, inertia, the "
-                   "seeds, every restart's inertia and the decoder's un-posed reconstruction of each centre")
-    p.add_argument("--cluster_labels", metavar="PATH.npy", help="with --cluster: also write the labels in the format --labels reads")
-    p.add_argument("--cluster_iters", type=int, default=None, metavar="I", help="Lloyd iterations per restart, I >= 1 (default 100; "
-                   "iterations after convergence change nothing)")
-    p.add_argument("--cluster_restarts", type=int, default=None, metavar="R", help="independent seedings, 1..%d (default 1); the one "
-                   "of lowest inertia is kept, the first of equals" % INFER_MAX_RESTARTS)
-    p.add_argument("--cluster_seed", type=int, default=None, metavar="S", help="seed of the generator the k-means++ uniforms come "
-                   "from (default --seed)")
-    args = p.parse_args(argv)
-    args.train_argv = train_argv
-    if args.cluster is None:
-        for name in ("cluster_out", "cluster_labels", "cluster_iters", "cluster_restarts", "cluster_seed"):
-            if getattr(args, name) is not None:
-                p.error("--%s needs --cluster" % name)
-    else:
-        if not 2 <= args.cluster <= INFER_MAX_CLUSTERS:
-            p.error("--cluster must be in [2, %d] (got %d)" % (INFER_MAX_CLUSTERS, args.cluster))
-        if args.labels is not None:
-            p.error("--cluster makes the classes itself: it excludes --labels")
-        if args.cluster_out is None:
-            p.error("--cluster needs --cluster_out")
-        if os.path.splitext(args.cluster_out)[1] != ".npz":
-            p.error("--cluster_out must end in .npz (got %s)" % args.cluster_out)
-        if args.cluster_labels is not None and os.path.splitext(args.cluster_labels)[1] != ".npy":
-            p.error("--cluster_labels must end in .npy (got %s)" % args.cluster_labels)
-        args.cluster_iters = 100 if args.cluster_iters is None else args.cluster_iters
-        args.cluster_restarts = 1 if args.cluster_restarts is None else args.cluster_restarts
-        args.cluster_seed = args.seed if args.cluster_seed is None else args.cluster_seed
-        if args.cluster_iters < 1:
-            p.error("--cluster_iters must be >= 1")
-        if not 1 <= args.cluster_restarts <= INFER_MAX_RESTARTS:
-            p.error("--cluster_restarts must be in [1, %d]" % INFER_MAX_RESTARTS)
-    if args.ctf_correct is not None and args.script != "particles":
-        p.error("--ctf_correct is for particles (the script whose images have a CTF), not %s" % args.script)
-    if args.ctf_correct == "flip" and args.aligned is None and args.class_averages is None:
-        p.error("--ctf_correct flip needs one of --aligned, --class_averages")
-    if args.ctf_correct == "wiener" and args.class_averages is None:
-        p.error("--ctf_correct wiener needs --class_averages")
-    if args.wiener_lambda is not None:
-        if args.ctf_correct != "wiener":
-            p.error("--wiener_lambda needs --ctf_correct wiener")
-        if not 0 <= args.wiener_lambda < float("inf"):
-            p.error("--wiener_lambda must be a finite number >= 0 (got %r)" % args.wiener_lambda)
-    elif args.ctf_correct == "wiener":
-        args.wiener_lambda = 1.0
-    if args.num_samples < 1:
-        p.error("--num_samples must be >= 1")
-    if not 1 <= args.chunk <= INFER_MAX_CHUNK:
-        p.error("--chunk must be in [1, %d]" % INFER_MAX_CHUNK)
-    if args.minibatch_size < 1:
-        p.error("--minibatch_size must be >= 1")
-    sav = args.generator is not None or args.inference is not None
-    if (args.state is None) == (not sav):
-        p.error("give either --state or --generator with --inference")
-    if sav and (args.generator is None or args.inference is None):
-        p.error("--generator and --inference go together")
-    if sav and train_argv is None:
-        p.error("--generator/--inference need the training script's flags after `--`")
-    if not sav and train_argv:
-        p.error("--state carries the training arguments: nothing may follow `--`")
-    for path in (args.state, args.generator, args.inference):
-        if path is not None and not os.path.isfile(path):
-            p.error("no such file: %s" % path)
-    for name in ("aligned", "recon"):
-        path = getattr(args, name)
-        if path is not None and os.path.splitext(path)[1] not in INFER_STACK_FORMATS:
-            p.error("--%s must end in .npy or .mrcs (got %s)" % (name, path))
-    if args.class_averages is not None and os.path.splitext(args.class_averages)[1] != ".npz":
-        p.error("--class_averages must end in .npz (got %s)" % args.class_averages)
-    if args.labels is not None and args.class_averages is None:
-        p.error("--labels needs --class_averages")
-    if args.aligned is None and args.recon is None and args.class_averages is None:
-        for name in ("pose", "interp"):
-            if getattr(args, name) is not None and not (name == "pose" and args.cluster is not None):
-                p.error("--%s needs one of --aligned, --recon, --class_averages" % name)
-    args.pose, args.interp = args.pose or "iw", args.interp or "bicubic"
-    args.label_array = None
-    if args.labels is not None:
-        try:
-            args.label_array = read_labels(args.labels)
-        except ValueError as e:
-            p.error(str(e))
-    return args
-
-
-def read_labels(path):
-    """The int64 class labels of a --labels file; ValueError with the reason when it is no 1-D integer .npy with values >= -1
-    and at most INFER_MAX_CLASSES classes."""
-    if not os.path.isfile(path):
-        raise ValueError("no such file: %s" % path)
-    try:
-        labels = np.load(path, allow_pickle=False)
-    except Exception as e:
-        raise ValueError("--labels %s is not a .npy array: %s" % (path, e))
-    if not isinstance(labels, np.ndarray) or labels.dtype.kind not in "iu":
-        raise ValueError("--labels %s must be an integer array (got %s)" % (path, getattr(labels, "dtype", type(labels).__name__)))
-    if labels.ndim != 1:
-        raise ValueError("--labels %s must be 1-D, one entry per image (got shape %s)" % (path, labels.shape))
-    labels = labels.astype(np.int64)
-    if labels.size and labels.min() < -1:
-        raise ValueError("--labels %s has a value below -1 (%d)" % (path, labels.min()))
-    if labels.size and labels.max() + 1 > INFER_MAX_CLASSES:
-        raise ValueError("--labels %s has %d classes, at most %d are supported" % (path, labels.max() + 1, INFER_MAX_CLASSES))
-    return labels
-
-
-def _refuse(message):
-    print("infer.py: " + message, file=sys.stderr)
-    raise SystemExit(2)
-
-
-def stored_namespace(ck, defaults, script):
-    """The training run's argument namespace from a state file: the stored arguments over RESUME_ARG_DEFAULTS over the
-    script's own defaults.  A file another script wrote names arguments this script's parser does not have (and lacks some it
-    has): refused, exit code 2."""
-    import argparse
-    stored = dict(ck["args"])
-    unknown = sorted(set(stored) - set(defaults))
-    missing = sorted(set(defaults) - set(stored) - set(RESUME_ARG_DEFAULTS))
-    if unknown or missing:
-        _refuse("the state file was not written by train_{}.py: it has the arguments {} which that script lacks, and lacks {}"
-                .format(script, unknown, missing))
-    return argparse.Namespace(**dict(defaults, **dict(RESUME_ARG_DEFAULTS, **stored)))
-
-
-def write_atomically(path, save):
-    """save(f) writes the open binary file f; the file is written under a temporary name beside `path` and renamed over it: an
-    interrupted write leaves no file under the final name."""
-    tmp = "{}.tmp{}".format(path, os.getpid())
-    try:
-        with open(tmp, "wb") as f:
-            save(f)
-        os.replace(tmp, path)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-    return path
-
-
-def write_npz(path, arrays):
-    """One .npz of plain arrays, written under a temporary name beside `path` and renamed over it."""
-    return write_atomically(path, lambda f: np.savez(f, **arrays))
-
-
-def write_stack(path, stack):
-    """An image stack (images, rows, cols, C) float32 as .npy, or as an MRC stack (C == 1), by the path's extension."""
-    if path.endswith(".mrcs"):
-        from . import mrc
-        return write_atomically(path, lambda f: mrc.write(f, stack[..., 0]))
-    return write_atomically(path, lambda f: np.save(f, stack))
-
-
-def read_npz(path):
-    with np.load(path, allow_pickle=False) as f:
-        return {k: f[k] for k in f.files}
-
-
-def score_arrays(per_image, q_mu, q_std, rotate, translate):
-    """The named arrays of infer.py's output from the rows of elbo.score_minibatch (host arrays): theta_* iff the model rotates,
-    dx_* iff it translates."""
-    inf_dim = q_mu.shape[1]
-    off = 1 if rotate else 0
-    c0 = off + (2 if translate else 0)
-    iw, best = per_image[:, 6:6 + inf_dim], per_image[:, 6 + inf_dim:6 + 2 * inf_dim]
-    out = {"bound": per_image[:, 0], "loglik": per_image[:, 1], "kl": per_image[:, 2], "ess": per_image[:, 3]}
-    if rotate:
-        out.update(theta_q=q_mu[:, 0], theta_q_std=q_std[:, 0], theta_iw=iw[:, 0], theta_R=per_image[:, 5], theta_best=best[:, 0])
-    if translate:
-        out.update(dx_q=q_mu[:, off:c0], dx_q_std=q_std[:, off:c0], dx_iw=iw[:, off:c0], dx_best=best[:, off:c0])
-    out.update(z_q=q_mu[:, c0:], z_q_std=q_std[:, c0:], z_iw=iw[:, c0:], z_best=best[:, c0:])
-    out["index"] = np.arange(per_image.shape[0], dtype=np.int64)
-    return {k: np.ascontiguousarray(v) for k, v in out.items()}
-
-
-def infer_main(args, parser_fn, build, positional=()):
-    """infer.py after its own parsing.  parser_fn(argv) is the training script's parser, build(args, device) its dataset and
-    network builder, `positional` stand-ins for its positional arguments when only its defaults are wanted."""
-    import json
-    script = args.script
-    rule = SCRIPTS[script]
-    ck = None
-    overridden = [n for n in INFER_PATH_OVERRIDES if getattr(args, n) is not None]
-    if args.state is not None:
-        try:
-            ck = read_checkpoint(args.state)
-        except CheckpointError as e:
-            _refuse(str(e).replace("--resume: ", ""))
-        targs = stored_namespace(ck, vars(parser_fn(list(positional))), script)
-        for n in overridden:
-            if not hasattr(targs, n):
-                _refuse("train_{}.py has no --{} to override".format(script, n))
-            setattr(targs, n, getattr(args, n))
-        completed = int(ck["completed"])
-    else:
-        targs = parser_fn(args.train_argv)
-        completed = targs.num_epochs
-    device = pick_device(args.device)
-    if targs.seed is not None:                      # build() must make the split the run trained on (galaxy shuffles in it)
-        torch.manual_seed(targs.seed)
-        np.random.seed(targs.seed % (2 ** 32))
-    if targs.gemm:
-        from . import _lib
-        _lib.set_gemm_mode(targs.gemm)
-    cfg = build(targs, device)
-    if ck is not None:
-        if not overridden:
-            try:
-                check_resume_fingerprint(ck, dataset_fingerprint(cfg["y_train"], cfg["y_test"]))
-            except CheckpointError as e:
-                _refuse(str(e).replace("--resume: ", ""))
-        try:
-            cfg["p_net"].load_state_dict(ck["train_step"]["p_net"])
-            cfg["q_net"].load_state_dict(ck["train_step"]["q_net"])
-        except (RuntimeError, KeyError) as e:
-            _refuse("the state file's networks do not fit what train_{}.py builds from its arguments: {}".format(
-                script, str(e).splitlines()[0]))
-        p_net, q_net = cfg["p_net"], cfg["q_net"]
-    else:
-        p_net = torch.load(args.generator, map_location="cpu", weights_only=False)
-        q_net = torch.load(args.inference, map_location="cpu", weights_only=False)
-    p_net, q_net = p_net.to(device).eval(), q_net.to(device).eval()
-    rotate, translate = cfg["rotate"], cfg["translate"]
-    z_scale = (0 if completed < getattr(targs, "z_delay", 0) else 1) if rule.z_schedule else 1
-    data = cfg["y_" + args.split].to(device)
-    ctf = cfg.get("ctf_" + args.split)
-    ctf = ctf.to(device) if ctf is not None else None
-    mask = cfg.get("mask")
-    mask = mask.to(device) if mask is not None else None
-    x = coord_grid(cfg["n"], cfg["m"]).to(device)
-    inf_dim = q_net.latent_dim
-    K, bs = args.num_samples, args.minibatch_size
-    # the optional image outputs (--aligned, --recon, --class_averages); getattr: a caller's namespace from before they existed
-    want = {k: getattr(args, k, None) for k in ("aligned", "recon", "class_averages")}
-    images, n, m = data.size(0), cfg["n"], cfg["m"]
-    channels = data[0].numel() // (n * m) if images else 1
-    labels = getattr(args, "label_array", None)
-    cluster = getattr(args, "cluster", None)        # --cluster K: the classes come from k-means of the content latents
-    if cluster is not None:
-        z_dim = inf_dim - (1 if rotate else 0) - (2 if translate else 0)
-        if z_dim < 1:
-            _refuse("--cluster groups the content latents, and this model has none (z_dim = 0)")
-        if z_scale == 0:
-            _refuse("--cluster: this state is from before the run's z_delay ended (z_scale = 0): every content latent is 0")
-        if cluster > images:
-            _refuse("--cluster {} exceeds the {} images of the {} split".format(cluster, images, args.split))
-    if labels is not None and labels.shape[0] != images:
-        _refuse("--labels has {} entries, the {} split has {} images".format(labels.shape[0], args.split, images))
-    for k in ("aligned", "recon"):
-        if want[k] is not None and want[k].endswith(".mrcs") and channels != 1:
-            _refuse("--{} {}: an MRC stack holds one channel, these images have {}".format(k, want[k], channels))
-    stacks = {k: torch.empty(images, n * m * channels, dtype=torch.float32, pin_memory=True)      # filled by non-blocking copies
-              for k in ("aligned", "recon") if want[k] is not None}
-    sums = None
-    label_d = None
-    if want["class_averages"] is not None:
-        if cluster is not None:
-            n_classes = cluster                     # the labels arrive on the device, after the scoring pass
-        else:
-            if labels is None:
-                labels = np.zeros(images, np.int64)     # one class holding every image
-            n_classes = max(int(labels.max()) + 1, 1) if images else 1
-            label_d = torch.from_numpy(labels.astype(np.int32)).to(device)
-        sums = ops.ClassSums(n_classes, n * m, channels, device)
-    # --ctf_correct: each image through its own transfer function (the table rows of the split, uploaded once) before it is aligned
-    correct = getattr(args, "ctf_correct", None)
-    table_d = wiener = None
-    if correct is not None:
-        table = cfg.get("ctf_params_" + args.split)
-        if table is None:
-            _refuse("--ctf_correct needs the CTF parameters of the {0} split: the run has no --ctf-{0} table".format(args.split))
-        if table.shape[0] < images:
-            _refuse("the CTF table of the {} split has {} rows, the split has {} images".format(args.split, table.shape[0], images))
-        if channels != 1:
-            _refuse("--ctf_correct takes one-channel images, these have {}".format(channels))
-        if rotate and n != m:
-            _refuse("--ctf_correct on a model that rotates needs a square box (the transfer function commutes with the rotation "
-                    "only there); these images are {}x{}".format(n, m))
-        table_d = torch.from_numpy(np.ascontiguousarray(table[:images], dtype=np.float64)).to(device)
-        ctf_scale = cfg["ctf_scale"]
-        if correct == "wiener":     # numerator: class sums of the aligned H*y; denominator: class sums of H^2
-            wiener = (ops.ClassSums(sums.n_classes, n * m, 1, device), ops.CtfPower(sums.n_classes, n, m, device, scale=ctf_scale))
-    gen = torch.Generator()
-    gen.manual_seed(args.seed)
-    rows = []
-
-    def align_and_update(lo, y, per_image, q_mu, labelled):
-        """One minibatch brought into the canonical frame; with `labelled` also its class-sum and Wiener updates under label_d.
-        The scoring walk and --cluster's second walk both make exactly these calls, in this order."""
-        seen = y if correct != "flip" else ops.ctf_apply(y, table_d[lo:lo + bs], n, m, ctf_scale, "flip")
-        aligned, cover = E.align_minibatch(seen, n, m, per_image, q_mu, rotate, translate, args.pose, args.interp)
-        if labelled and wiener is not None:
-            g = ops.ctf_apply(y, table_d[lo:lo + bs], n, m, ctf_scale, "multiply")
-            g, g_cover = E.align_minibatch(g, n, m, per_image, q_mu, rotate, translate, args.pose, args.interp)
-            wiener[0].update(g, g_cover, label_d[lo:lo + bs])
-            wiener[1].update(table_d[lo:lo + bs], label_d[lo:lo + bs])
-        if labelled:
-            sums.update(aligned, cover, label_d[lo:lo + bs])
-        return aligned
-
-    labelled = sums is not None and cluster is None     # --cluster: the labels do not exist yet, the updates wait for them
-    for lo in range(0, images, bs):                 # dataset order, nothing read back inside the loop
-        y = data[lo:lo + bs]
-        noise = torch.empty(y.size(0) * K, inf_dim).normal_(generator=gen).to(device, non_blocking=True)
-        out = E.score_minibatch(script, x, y, p_net, q_net, num_samples=K, chunk=min(args.chunk, K), rotate=rotate,
-                                translate=translate, dx_scale=targs.dx_scale, theta_prior=targs.theta_prior, z_scale=z_scale,
-                                mask=mask, ctf=None if ctf is None else ctf[lo:lo + bs], noise=noise)
-        rows.append(torch.cat([out["per_image"], out["q_mu"], out["q_std"]], 1))
-        if "aligned" in stacks or labelled:
-            aligned = align_and_update(lo, y, out["per_image"], out["q_mu"], labelled)
-            if "aligned" in stacks:
-                stacks["aligned"][lo:lo + bs].copy_(aligned.view(y.size(0), -1), non_blocking=True)
-        if "recon" in stacks:
-            zc = E.content_latents(out["per_image"], out["q_mu"], rotate, translate, args.pose)
-            recon = E.reconstruct_unposed(x, p_net, y.size(0), zc, gaussian_mean=(script == "particles"))
-            stacks["recon"][lo:lo + bs].copy_(recon.reshape(y.size(0), -1), non_blocking=True)
-    width = 6 + 2 * inf_dim
-    fit = None
-    if cluster is not None:
-        # k-means of every image's content latents, then (for --class_averages) a second walk over the minibatches that re-aligns
-        # from the stored rows and makes the update calls the scoring pass would have made, in its order; no host read in between
-        all_rows = torch.cat(rows)
-        zc = E.content_latents(all_rows[:, :width], all_rows[:, width:width + inf_dim], rotate, translate, args.pose)
-        kgen = torch.Generator()
-        kgen.manual_seed(args.cluster_seed)
-        fit = E.cluster_latents(zc, cluster, args.cluster_iters, args.cluster_restarts, kgen)
-        label_d = fit["label"]
-        if sums is not None:
-            for i, lo in enumerate(range(0, images, bs)):
-                align_and_update(lo, data[lo:lo + bs], rows[i][:, :width], rows[i][:, width:width + inf_dim], True)
-        centre_recon = E.reconstruct_unposed(x, p_net, cluster, fit["centres"].float(), gaussian_mean=(script == "particles"))
-    host = torch.cat(rows).cpu().numpy()            # the one transfer of the scores
-    if stacks:
-        torch.cuda.synchronize(device)              # the one synchronisation: every minibatch's copy has landed
-    arrays = score_arrays(host[:, :width], host[:, width:width + inf_dim], host[:, width + inf_dim:], rotate, translate)
-    means = [float(np.mean(arrays[k], dtype=np.float64)) for k in ("bound", "loglik", "kl")]
-    meta = {"script": script, "state": args.state, "generator": args.generator, "inference": args.inference, "num_samples": K,
-            "chunk": args.chunk, "seed": args.seed, "split": args.split, "images": int(host.shape[0]),
-            "mean_bound": means[0], "mean_loglik": means[1], "mean_kl": means[2]}
-    if any(v is not None for v in want.values()):   # only then: without the options the file is what it always was
-        meta.update(pose=args.pose, interp=args.interp, labels=args.labels, **want)
-    if correct is not None:
-        meta.update(ctf_correct=correct, wiener_lambda=args.wiener_lambda)
-    if cluster is not None:
-        meta.update(pose=args.pose, cluster=cluster, cluster_out=args.cluster_out, cluster_labels=args.cluster_labels,
-                    cluster_iters=args.cluster_iters, cluster_restarts=args.cluster_restarts, cluster_seed=args.cluster_seed)
-        labels = fit["label"].cpu().numpy().astype(np.int64)
-        record = ops.KMeans.read_record(fit["record"])
-        found = {"label": labels, "centres": fit["centres"].cpu().numpy(), "members": fit["members"].cpu().numpy(),
-                 "inertia": np.float64(record["inertia"]), "iterations": np.int64(record["iterations"]),
-                 "converged_at": np.int64(record["converged_at"]), "seed_index": fit["seed_index"].cpu().numpy().astype(np.int64),
-                 "restart_inertia": fit["restart_inertia"].cpu().numpy(), "chosen_restart": np.int64(fit["chosen_restart"].item()),
-                 "centre_recon": centre_recon.cpu().numpy().reshape(cluster, n, m, -1), "meta": np.array(json.dumps(meta))}
-    arrays["meta"] = np.array(json.dumps(meta))
-    for k, stack in stacks.items():
-        write_stack(want[k], stack.numpy().reshape(images, n, m, channels))
-    if sums is not None:
-        total, count = (t.cpu().numpy() for t in sums.result())
-        total, count = total.reshape(sums.n_classes, n, m, channels), count.reshape(sums.n_classes, n, m)
-        average = np.divide(total, count[..., None], out=np.zeros_like(total), where=count[..., None] > 0).astype(np.float32)
-        members = np.bincount(labels[labels >= 0], minlength=sums.n_classes).astype(np.int64)
-        classes = {"sum": total, "count": count, "average": average, "members": members}
-        if wiener is not None:      # numerator and denominator too: another lambda needs no second run
-            w_sum, w_den = wiener[0].result()[0], wiener[1].result()
-            w_avg = ops.wiener_finish(w_sum, w_den, args.wiener_lambda, n, m)
-            classes.update(wiener_sum=w_sum.cpu().numpy().reshape(sums.n_classes, n, m, 1), wiener_den=w_den.cpu().numpy(),
-                           wiener_average=w_avg.cpu().numpy().reshape(sums.n_classes, n, m, 1),
-                           wiener_lambda=np.float64(args.wiener_lambda))
-        write_npz(want["class_averages"], classes)
-    if cluster is not None:
-        write_npz(args.cluster_out, found)
-        if args.cluster_labels is not None:
-            write_atomically(args.cluster_labels, lambda f: np.save(f, labels))
-    write_npz(args.out, arrays)
-    print("images {}\tbound {!r}\tlog p(x|z) {!r}\tKL {!r}\tmedian ESS {:.3f}".format(
-        host.shape[0], means[0], means[1], means[2], float(np.median(arrays["ess"]))))
-    return 0

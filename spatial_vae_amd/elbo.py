@@ -14,6 +14,7 @@ augmentation angles (radians) instead of the np.random draw.
 with the device restatement of Pillow's bicubic Image.rotate (ops.rotate_augment) instead of a per-image PIL loop on
 the host; the angles come from np.random exactly as in the reference.
 """
+import collections
 import math
 
 import numpy as np
@@ -185,6 +186,20 @@ def eval_minibatch_particles(x, y, mask, ctf, p_net, q_net, rotate=True, transla
 
 
 # ---------------------------------------------------------------- per-image scoring (infer.py)
+RowLayout = collections.namedtuple("RowLayout", "theta dx content z_dim inf_dim iw best width")
+
+
+def row_layout(rotate, translate, inf_dim):
+    """Where things are in what score_minibatch returns, the one statement of it.  theta, dx, content: the column slices of a
+    latent row (inf_dim wide: "q_mu", "q_std", the noise), theta and dx empty when the model has no such coordinate; z_dim: the
+    width of content.  iw, best: the slices of a "per_image" row (as svae_iw_stream_finish lays it out, `width` = 6 + 2 * inf_dim
+    columns) that hold the importance-weighted mean and the best sample, each one latent row."""
+    off = 1 if rotate else 0
+    c0 = off + (2 if translate else 0)
+    return RowLayout(slice(0, off), slice(off, c0), slice(c0, inf_dim), inf_dim - c0, inf_dim,
+                     slice(6, 6 + inf_dim), slice(6 + inf_dim, 6 + 2 * inf_dim), 6 + 2 * inf_dim)
+
+
 @torch.no_grad()
 def score_minibatch(script, x, y, p_net, q_net, *, num_samples, chunk, rotate, translate, dx_scale, theta_prior, z_scale=1,
                     mask=None, ctf=None, noise=None, return_best=False):
@@ -224,17 +239,16 @@ def score_minibatch(script, x, y, p_net, q_net, *, num_samples, chunk, rotate, t
         _, _, loglik = _decode_score(script, x, y_k, p_net, B * kc, theta, dx, zc, mask, ctf_k)
         stream.update(rotate, translate, script == "mnist", dx_scale, z_scale, theta_prior, kc, loglik, log_ratio, theta, dx, zc)
     per_image, out3 = stream.finish()
-    off = 1 if rotate else 0
-    c0 = off + (2 if translate else 0)
+    lay = row_layout(rotate, translate, inf_dim)
     unit = torch.ones(inf_dim, device=q_out.device)
-    unit[off:c0] = float(dx_scale)
-    unit[c0:] = float(z_scale)
+    unit[lay.dx] = float(dx_scale)
+    unit[lay.content] = float(z_scale)
     out = {"per_image": per_image, "out3": out3, "q_mu": q_out[:, :inf_dim] * unit, "q_std": torch.exp(q_out[:, inf_dim:]) * unit}
     if return_best:
-        best = per_image[:, 6 + inf_dim:]
+        best = per_image[:, lay.best]
         theta = best[:, 0].contiguous() if rotate else None
-        dx = best[:, off:c0].contiguous() if translate else None
-        zc = best[:, c0:].contiguous()
+        dx = best[:, lay.dx].contiguous() if translate else None
+        zc = best[:, lay.content].contiguous()
         out["y_best"] = _decode_score(script, x, y, p_net, B, theta, dx, zc, mask, ctf)[0]
     return out
 
@@ -242,12 +256,11 @@ def score_minibatch(script, x, y, p_net, q_net, *, num_samples, chunk, rotate, t
 POSES = ("iw", "best", "q")     # which estimate of an image's pose and content: the importance-weighted mean, the best sample, q's mean
 
 
-def _pose_rows(per_image, q_mu, pose):
+def _pose_rows(per_image, q_mu, pose, lay):
     """The (B, inf_dim) latent rows of one estimate out of what score_minibatch returned, in the decoder's units."""
     if pose not in POSES:
         raise RuntimeError("pose must be one of %s, got %r" % (POSES, pose))
-    inf_dim = q_mu.size(1)
-    return {"iw": per_image[:, 6:6 + inf_dim], "best": per_image[:, 6 + inf_dim:6 + 2 * inf_dim], "q": q_mu}[pose]
+    return {"iw": per_image[:, lay.iw], "best": per_image[:, lay.best], "q": q_mu}[pose]
 
 
 @torch.no_grad()
@@ -255,17 +268,17 @@ def align_minibatch(y, rows, cols, per_image, q_mu, rotate, translate, pose="iw"
     """The minibatch's observed images brought into the model's canonical frame (ops.align_images) at the pose estimate
     `pose` (POSES) taken from score_minibatch's "per_image" and "q_mu": device slices, nothing is read back.  Returns (aligned,
     shaped like y; cover (B, rows*cols) uint8).  A model with neither rotation nor translation gets its images back."""
-    lat = _pose_rows(per_image, q_mu, pose)
-    off = 1 if rotate else 0
+    lay = row_layout(rotate, translate, q_mu.size(1))
+    lat = _pose_rows(per_image, q_mu, pose, lay)
     theta = lat[:, 0].contiguous() if rotate else None
-    dx = lat[:, off:off + 2].contiguous() if translate else None
+    dx = lat[:, lay.dx].contiguous() if translate else None
     return ops.align_images(y, theta, dx, rows, cols, interp)
 
 
 def content_latents(per_image, q_mu, rotate, translate, pose="iw"):
     """The content part (B, z_dim) of the same estimate: what reconstruct_unposed decodes."""
-    c0 = (1 if rotate else 0) + (2 if translate else 0)
-    return _pose_rows(per_image, q_mu, pose)[:, c0:].contiguous()
+    lay = row_layout(rotate, translate, q_mu.size(1))
+    return _pose_rows(per_image, q_mu, pose, lay)[:, lay.content].contiguous()
 
 
 @torch.no_grad()

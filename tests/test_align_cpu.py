@@ -17,9 +17,9 @@ INTERPS = ["bicubic", "bilinear"]
 POSES = [(0.7, (0.12, -0.08)), (-2.3, (-0.1, 0.15))]
 
 
-def _cli():
-    from spatial_vae_amd import cli
-    return cli
+def _infer():
+    from spatial_vae_amd import infer
+    return infer
 
 
 # ---------------------------------------------------------------- the header and its table
@@ -180,16 +180,16 @@ def test_class_sum_reference_against_a_naive_loop():
 def test_new_options_default_to_off(tmp_path):
     state = tmp_path / "a.ckpt"
     state.write_bytes(b"x")
-    a = _cli().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz"])
+    a = _infer().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz"])
     assert (a.aligned, a.recon, a.class_averages, a.labels, a.label_array) == (None, None, None, None, None)
     assert (a.pose, a.interp) == ("iw", "bicubic")
     labels = tmp_path / "l.npy"
     np.save(labels, np.array([0, 2, -1, 1], np.int16))
-    a = _cli().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz", "--aligned", "a.mrcs", "--recon", "r.npy", "--class_averages",
+    a = _infer().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz", "--aligned", "a.mrcs", "--recon", "r.npy", "--class_averages",
                                 "c.npz", "--labels", str(labels), "--pose", "best", "--interp", "bilinear"])
     assert (a.aligned, a.recon, a.class_averages, a.pose, a.interp) == ("a.mrcs", "r.npy", "c.npz", "best", "bilinear")
     assert a.label_array.dtype == np.int64 and a.label_array.tolist() == [0, 2, -1, 1]
-    a = _cli().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz", "--class_averages", "c.npz", "--pose", "q"])
+    a = _infer().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz", "--class_averages", "c.npz", "--pose", "q"])
     assert (a.pose, a.interp, a.label_array) == ("q", "bicubic", None)
 
 

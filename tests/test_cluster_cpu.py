@@ -15,9 +15,9 @@ from test_binding_cpu import SCALARS, _allowed, binding_constants, parse_header
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _cli():
-    from spatial_vae_amd import cli
-    return cli
+def _infer():
+    from spatial_vae_amd import infer
+    return infer
 
 
 # ---------------------------------------------------------------- the header and its table
@@ -138,15 +138,15 @@ def _base(tmp_path):
 
 def test_cluster_options_default_to_off_and_fill_in(tmp_path):
     base = _base(tmp_path)
-    a = _cli().infer_arguments(base)
+    a = _infer().infer_arguments(base)
     assert (a.cluster, a.cluster_out, a.cluster_labels, a.cluster_iters, a.cluster_restarts, a.cluster_seed) == (None,) * 6
-    a = _cli().infer_arguments(base + ["--seed", "7", "--cluster", "3", "--cluster_out", "k.npz"])
+    a = _infer().infer_arguments(base + ["--seed", "7", "--cluster", "3", "--cluster_out", "k.npz"])
     assert (a.cluster, a.cluster_out, a.cluster_labels, a.cluster_iters, a.cluster_restarts, a.cluster_seed) == (3, "k.npz", None, 100, 1, 7)
     assert a.pose == "iw" and a.class_averages is None
-    a = _cli().infer_arguments(base + ["--cluster", "1024", "--cluster_out", "k.npz", "--cluster_labels", "l.npy", "--cluster_iters", "1",
+    a = _infer().infer_arguments(base + ["--cluster", "1024", "--cluster_out", "k.npz", "--cluster_labels", "l.npy", "--cluster_iters", "1",
                                        "--cluster_restarts", "16", "--cluster_seed", "5", "--pose", "q"])       # --pose with --cluster alone
     assert (a.cluster, a.cluster_labels, a.cluster_iters, a.cluster_restarts, a.cluster_seed, a.pose) == (1024, "l.npy", 1, 16, 5, "q")
-    assert _cli().INFER_MAX_CLUSTERS == 1024 <= _cli().INFER_MAX_CLASSES
+    assert _infer().INFER_MAX_CLUSTERS == 1024 <= _infer().INFER_MAX_CLASSES
 
 
 REFUSALS = [
@@ -175,7 +175,7 @@ def test_cluster_refusals_are_made_by_the_parser(tmp_path, capsys, extra, messag
     np.save(tmp_path / "int1d.npy", np.array([0, 1, 1]))
     argv = _base(tmp_path) + [a.format(int1d=tmp_path / "int1d.npy") for a in extra]
     with pytest.raises(SystemExit) as e:
-        _cli().infer_arguments(argv)
+        _infer().infer_arguments(argv)
     assert e.value.code == 2 and message in capsys.readouterr().err
 
 

@@ -15,9 +15,9 @@ from test_binding_cpu import _allowed, binding_constants, parse_header
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _cli():
-    from spatial_vae_amd import cli
-    return cli
+def _infer():
+    from spatial_vae_amd import infer
+    return infer
 
 
 def _golden_table():
@@ -150,13 +150,13 @@ def test_ctf_options_default_to_off(tmp_path):
     state = tmp_path / "a.ckpt"
     state.write_bytes(b"x")
     base = ["particles", "--state", str(state), "--out", "s.npz"]
-    a = _cli().infer_arguments(base)
+    a = _infer().infer_arguments(base)
     assert (a.ctf_correct, a.wiener_lambda) == (None, None)
-    a = _cli().infer_arguments(base + ["--ctf_correct", "flip", "--aligned", "a.npy"])
+    a = _infer().infer_arguments(base + ["--ctf_correct", "flip", "--aligned", "a.npy"])
     assert (a.ctf_correct, a.wiener_lambda) == ("flip", None)
-    a = _cli().infer_arguments(base + ["--ctf_correct", "wiener", "--class_averages", "c.npz"])
+    a = _infer().infer_arguments(base + ["--ctf_correct", "wiener", "--class_averages", "c.npz"])
     assert (a.ctf_correct, a.wiener_lambda) == ("wiener", 1.0)
-    a = _cli().infer_arguments(base + ["--ctf_correct", "wiener", "--class_averages", "c.npz", "--wiener_lambda", "0"])
+    a = _infer().infer_arguments(base + ["--ctf_correct", "wiener", "--class_averages", "c.npz", "--wiener_lambda", "0"])
     assert (a.ctf_correct, a.wiener_lambda) == ("wiener", 0.0)
 
 

@@ -75,7 +75,7 @@ def test_mnist_aligned_recon_and_class_averages(tmp_path):
     a, r, c = np.load(os.path.join(cwd, "a.npy")), np.load(os.path.join(cwd, "r.npy")), _npz(os.path.join(cwd, "c.npz"))
     assert a.shape == r.shape == (n, rows, cols, 1) and a.dtype == r.dtype == np.float32
     targs = train_mnist.mnist_arguments(train)
-    cfg = train_mnist.build(targs, torch.device("cpu"))             # the split, as infer_main obtains it
+    cfg = train_mnist.build(targs, torch.device("cpu"))             # the split, as infer.infer_main obtains it
     y = cfg["y_test"].numpy()
     fx, fy = source_positions(s["theta_iw"], s["dx_iw"], n, rows, cols)
     assert int(near_threshold(fx, fy, rows, cols).sum()) == 0

@@ -76,7 +76,7 @@ def test_particles_flip_and_wiener(tmp_path):
     assert (metas["t"]["ctf_correct"], metas["t"]["wiener_lambda"]) == ("wiener", 0.5)
     assert set(metas["s"]) - set(metas["p"]) == set(metas["t"]) - set(metas["p"]) == {"ctf_correct", "wiener_lambda"}
 
-    cfg = train_particles.build(train_particles.particle_arguments(train), torch.device("cuda:0"))      # the split, as infer_main has it
+    cfg = train_particles.build(train_particles.particle_arguments(train), torch.device("cuda:0"))      # the split, as infer.infer_main has it
     y = cfg["y_test"].numpy()
     table, scale = cfg["ctf_params_test"], cfg["ctf_scale"]
     assert np.array_equal(table, tables["te.txt"]) and scale == 1.0 and y.shape == (images, n * m)

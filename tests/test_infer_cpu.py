@@ -19,16 +19,21 @@ def _cli():
     return cli
 
 
+def _infer():
+    from spatial_vae_amd import infer
+    return infer
+
+
 def test_parser_defaults_and_the_split(tmp_path):
     state = tmp_path / "a.ckpt"
     state.write_bytes(b"x")
-    a = _cli().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz"])
+    a = _infer().infer_arguments(["mnist", "--state", str(state), "--out", "s.npz"])
     assert (a.script, a.split, a.num_samples, a.chunk, a.minibatch_size, a.seed, a.device) == ("mnist", "test", 64, 64, 100, 0, -2)
     assert a.train_argv is None and a.generator is None and a.train_path is None and a.ctf_test is None
     g, q = tmp_path / "g.sav", tmp_path / "q.sav"
     g.write_bytes(b"x")
     q.write_bytes(b"x")
-    a = _cli().infer_arguments(["particles", "--generator", str(g), "--inference", str(q), "--out", "s.npz", "--num_samples", "5000",
+    a = _infer().infer_arguments(["particles", "--generator", str(g), "--inference", str(q), "--out", "s.npz", "--num_samples", "5000",
                                 "--chunk", "50", "--", "tr.mrcs", "te.mrcs", "--z-dim", "4", "--out", "not-ours"])
     assert a.train_argv == ["tr.mrcs", "te.mrcs", "--z-dim", "4", "--out", "not-ours"] and a.out == "s.npz"
     assert (a.num_samples, a.chunk, a.state) == (5000, 50, None)
@@ -65,35 +70,35 @@ def test_state_file_of_another_script_is_refused(tmp_path):
     device is picked."""
     import train_galaxy
     import train_mnist
-    cli = _cli()
+    cli, infer = _cli(), _infer()
     stored = cli.plain_args(train_galaxy.galaxy_arguments(["a.npy", "b.npy", "--synthetic", "8"]))
     with pytest.raises(SystemExit) as e:
-        cli.stored_namespace({"args": stored}, vars(train_mnist.mnist_arguments([])), "mnist")
+        infer.stored_namespace({"args": stored}, vars(train_mnist.mnist_arguments([])), "mnist")
     assert e.value.code == 2
     mine = cli.plain_args(train_mnist.mnist_arguments(["--z_dim", "5"]))
     for k in cli.RESUME_ARG_DEFAULTS:          # a file from before these options existed
         mine.pop(k)
-    ns = cli.stored_namespace({"args": mine}, vars(train_mnist.mnist_arguments([])), "mnist")
+    ns = infer.stored_namespace({"args": mine}, vars(train_mnist.mnist_arguments([])), "mnist")
     assert ns.z_dim == 5 and ns.num_samples == 1 and ns.clip_grad_norm is None
 
 
 def test_npz_round_trip_and_interrupted_write(tmp_path, monkeypatch):
-    cli = _cli()
+    infer = _infer()
     rs = np.random.RandomState(0)
     per_image = rs.normal(size=(7, 6 + 2 * 6)).astype(np.float32)
     q_mu, q_std = rs.normal(size=(7, 6)).astype(np.float32), rs.uniform(size=(7, 6)).astype(np.float32)
-    arrays = cli.score_arrays(per_image, q_mu, q_std, True, True)
+    arrays = infer.score_arrays(per_image, q_mu, q_std, True, True)
     arrays["meta"] = np.array(json.dumps({"k": 1}))
     path = str(tmp_path / "s.npz")
-    cli.write_npz(path, arrays)
-    back = cli.read_npz(path)                                   # allow_pickle=False: plain arrays only
+    infer.write_npz(path, arrays)
+    back = infer.read_npz(path)                                   # allow_pickle=False: plain arrays only
     assert sorted(back) == sorted(arrays) and all(np.array_equal(back[k], arrays[k]) for k in arrays)
     assert json.loads(str(back["meta"])) == {"k": 1} and os.listdir(tmp_path) == ["s.npz"]
     assert np.array_equal(back["theta_iw"], per_image[:, 6]) and np.array_equal(back["dx_best"], per_image[:, 13:15])
     assert np.array_equal(back["z_q"], q_mu[:, 3:]) and np.array_equal(back["theta_R"], per_image[:, 5])
-    no_rot = cli.score_arrays(per_image[:, :6 + 2 * 5], q_mu[:, :5], q_std[:, :5], False, True)
+    no_rot = infer.score_arrays(per_image[:, :6 + 2 * 5], q_mu[:, :5], q_std[:, :5], False, True)
     assert not [k for k in no_rot if k.startswith("theta_")] and no_rot["dx_iw"].shape == (7, 2) and no_rot["z_iw"].shape == (7, 3)
-    no_dx = cli.score_arrays(per_image[:, :6 + 2 * 4], q_mu[:, :4], q_std[:, :4], True, False)
+    no_dx = infer.score_arrays(per_image[:, :6 + 2 * 4], q_mu[:, :4], q_std[:, :4], True, False)
     assert not [k for k in no_dx if k.startswith("dx_")] and no_dx["z_best"].shape == (7, 3)
 
     def broken(f, **kw):
@@ -102,10 +107,10 @@ def test_npz_round_trip_and_interrupted_write(tmp_path, monkeypatch):
     monkeypatch.setattr(np, "savez", broken)
     other = str(tmp_path / "t.npz")
     with pytest.raises(KeyboardInterrupt):
-        cli.write_npz(other, arrays)
+        infer.write_npz(other, arrays)
     with pytest.raises(KeyboardInterrupt):
-        cli.write_npz(path, arrays)                             # nor is an earlier file damaged
-    assert os.listdir(tmp_path) == ["s.npz"] and sorted(cli.read_npz(path)) == sorted(arrays)
+        infer.write_npz(path, arrays)                             # nor is an earlier file damaged
+    assert os.listdir(tmp_path) == ["s.npz"] and sorted(infer.read_npz(path)) == sorted(arrays)
 
 
 def test_reference_holds_to_properties_of_the_definitions():
