@@ -164,6 +164,16 @@ CLUSTER_SIGNATURES = {
 }
 
 
+# ---- include/svae_frc.h: Fourier ring correlation and the filter by per-ring weights, a sixth header with a table of its own ----
+# Same rules (tests/test_frc_cpu.py holds these rows to that header's prototypes).  The header adds no constant.
+FRC_SIGNATURES = {
+    "svae_frc_workspace_bytes": (sz, [i32, i32, i32]),
+    "svae_frc": (cint, [vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp, sz, vp]),
+    "svae_frc_filter_workspace_bytes": (sz, [i32, i32, i32]),
+    "svae_frc_filter": (cint, [vp, vp, i32, i32, i32, vp, vp, sz, vp]),
+}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -187,7 +197,7 @@ def lib():
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
     for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES,
-                                      **CLUSTER_SIGNATURES}.items():
+                                      **CLUSTER_SIGNATURES, **FRC_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

@@ -17,6 +17,7 @@
 #include "../../include/svae_align.h"
 #include "../../include/svae_ctfcorr.h"
 #include "../../include/svae_cluster.h"
+#include "../../include/svae_frc.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
@@ -24,6 +25,7 @@
 #include "iw_stream.h"
 #include "align.h"
 #include "ctfcorr.h"
+#include "frc.h"
 #include "cluster.h"
 #include "encoder.h"
 #include "split.h"
@@ -1861,6 +1863,55 @@ int svae_wiener_finish(const double* sum, const double* den, double lambda, int3
     if (!sum || !den || !average) return fail(SVAE_E_INVALID, "svae_wiener_finish: null sum, den or average");
     return dft_launch("svae_wiener_finish", wiener_finish_kernel<false>, wiener_finish_kernel<true>, n_classes, n, m, ws,
                       static_cast<hipStream_t>(stream), sum, den, lambda, (int)n_classes, (int)n, (int)m, average);
+}
+
+// ---- Fourier ring correlation (include/svae_frc.h) ----
+namespace {
+inline bool bytes_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + qn && b < a + pn;
+}
+// the size rules the two ring calls share, then ctfcorr's plane and workspace rules; 0 or the refusal
+int frc_check(const char* who, int planes, int n, int m, const void* ws, size_t ws_bytes) {
+    if (n < 2 || m < 2 || n > 1024 || m > 1024) return fail(SVAE_E_INVALID, "%s: n and m must be in 2..1024 (got %d x %d)", who, n, m);
+    if (planes < 1) return fail(SVAE_E_INVALID, "%s: planes must be positive (got %d)", who, planes);
+    return dft_check(who, planes, n, m, ws, ws_bytes);
+}
+}  // namespace
+
+size_t svae_frc_workspace_bytes(int32_t planes, int32_t n, int32_t m) { return dft_workspace_bytes(planes, n, m); }
+
+int svae_frc(const double* a, const double* b, int32_t planes, int32_t n, int32_t m, double mask_radius, double mask_edge,
+             double* sums, double* frc, int32_t* ring_count, void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (const int rc = frc_check("svae_frc", planes, n, m, ws, ws_bytes)) return rc;
+    if (!(mask_radius >= 0.0) || isinf(mask_radius)) return fail(SVAE_E_INVALID, "svae_frc: mask_radius must be finite and >= 0");
+    if (mask_radius > 0.0 && (!(mask_edge > 0.0) || isinf(mask_edge)))
+        return fail(SVAE_E_INVALID, "svae_frc: mask_edge must be finite and > 0 where mask_radius > 0");
+    if (!a || !b || !sums || !frc || !ring_count) return fail(SVAE_E_INVALID, "svae_frc: null a, b, sums, frc or ring_count");
+    const size_t R = (size_t)((n < m ? n : m) / 2 + 1);
+    const size_t in_bytes = (size_t)planes * n * m * sizeof(double);
+    const void* outs[3] = {sums, frc, ring_count};
+    const size_t out_bytes[3] = {(size_t)planes * R * 3 * sizeof(double), (size_t)planes * R * sizeof(double), R * sizeof(int32_t)};
+    for (int i = 0; i < 3; ++i)
+        if (bytes_overlap(a, in_bytes, outs[i], out_bytes[i]) || bytes_overlap(b, in_bytes, outs[i], out_bytes[i]))
+            return fail(SVAE_E_INVALID, "svae_frc: a and b must not overlap sums, frc or ring_count");
+    return dft_launch("svae_frc", frc_kernel<false>, frc_kernel<true>, planes, n, m, ws, static_cast<hipStream_t>(stream), a, b,
+                      (int)planes, (int)n, (int)m, mask_radius, mask_edge, sums, frc, reinterpret_cast<int*>(ring_count));
+}
+
+size_t svae_frc_filter_workspace_bytes(int32_t planes, int32_t n, int32_t m) { return dft_workspace_bytes(planes, n, m); }
+
+int svae_frc_filter(const double* x, const double* weight, int32_t planes, int32_t n, int32_t m, float* out, void* ws,
+                    size_t ws_bytes, svae_stream_t stream) {
+    if (const int rc = frc_check("svae_frc_filter", planes, n, m, ws, ws_bytes)) return rc;
+    if (!x || !weight || !out) return fail(SVAE_E_INVALID, "svae_frc_filter: null x, weight or out");
+    const size_t R = (size_t)((n < m ? n : m) / 2 + 1);
+    const size_t total = (size_t)planes * n * m;
+    if (bytes_overlap(x, total * sizeof(double), out, total * sizeof(float)) ||
+        bytes_overlap(weight, (size_t)planes * R * sizeof(double), out, total * sizeof(float)))
+        return fail(SVAE_E_INVALID, "svae_frc_filter: x and weight must not overlap out");
+    return dft_launch("svae_frc_filter", frc_filter_kernel<false>, frc_filter_kernel<true>, planes, n, m, ws,
+                      static_cast<hipStream_t>(stream), x, weight, (int)planes, (int)n, (int)m, out);
 }
 
 // ---- k-means over the content latents (include/svae_cluster.h) ----

@@ -303,6 +303,47 @@ def cluster_latents(points, k, iters, restarts=1, generator=None):
     return out
 
 
+def ring_layout(n, m):
+    """The rings of an n x m plane (include/svae_frc.h): (L, R, ring_frequency) with L = min(n, m), R = L // 2 + 1 rings and
+    ring r standing for ring_frequency[r] = r / L cycles per pixel."""
+    L = min(int(n), int(m))
+    R = L // 2 + 1
+    return L, R, np.arange(R, dtype=np.float64) / L
+
+
+def frc_weight(frc):
+    """The per-ring weight sqrt(2 f / (1 + f)) that takes a half-set FRC f to the full average's correlation with the signal;
+    0 where f <= 0.  A torch expression: on the device nothing is read back."""
+    f = torch.clamp(frc, min=0.0)
+    return torch.where(frc > 0, torch.sqrt(2.0 * f / (1.0 + f)), torch.zeros_like(frc))
+
+
+def frc_resolution(frc_row, threshold, L):
+    """(resolution in pixels, never_below) of one FRC curve (R) on the host: NaN where ring 0 is already below the threshold;
+    else at the first ring r >= 1 below it, L over the ring position interpolated linearly between r - 1 and r; else L / (R - 1),
+    the last ring, with never_below = True: the curve says no more than that."""
+    f = np.asarray(frc_row, dtype=np.float64)
+    t = float(threshold)
+    if not f[0] >= t:
+        return float("nan"), False
+    for r in range(1, f.shape[0]):
+        if f[r] < t:
+            with np.errstate(divide="ignore"):
+                return float(np.float64(L) / np.float64((r - 1) + (f[r - 1] - t) / (f[r - 1] - f[r]))), False
+    return float(L) / (f.shape[0] - 1), True
+
+
+def frc_mask_weights(n, m, radius, edge):
+    """The soft circular mask of svae_frc as its rule gives it, (n, m) float64 on the host; radius 0 = all ones."""
+    if radius == 0:
+        return np.ones((n, m), np.float64)
+    dy = np.arange(n, dtype=np.float64)[:, None] - 0.5 * (n - 1)
+    dx = np.arange(m, dtype=np.float64)[None, :] - 0.5 * (m - 1)
+    d = np.sqrt(dx * dx + dy * dy)
+    w = 0.5 * (1.0 + np.cos(np.pi * ((d - radius) / edge)))
+    return np.where(d <= radius, 1.0, np.where(d >= radius + edge, 0.0, w))
+
+
 def _decode_on_grid(x, p_net, B, zc):
     """The decoder on the un-posed grid at the content latents zc."""
     if hasattr(p_net, "forward_posed"):

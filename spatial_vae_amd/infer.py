@@ -2,8 +2,9 @@
 
 Its own command line (infer_arguments: every refusal that needs no data, made before the kernel library is loaded), its file
 writers, and infer_main: a short sequence of stages -- load the model, check the request against the split, allocate the
-accumulators, walk the minibatches scoring (and aligning) them, cluster, collect and write.  The device work is elbo.py's
-(score_minibatch, align_minibatch, reconstruct_unposed, cluster_latents) and ops.py's.
+accumulators, walk the minibatches scoring (and aligning) them, cluster, finish the half-set correlation (--frc), collect and
+write.  The device work is elbo.py's (score_minibatch, align_minibatch, reconstruct_unposed, cluster_latents, frc_weight) and
+ops.py's.
 """
 import collections
 import json
@@ -24,6 +25,9 @@ INFER_MAX_CLASSES = 4096    # classes of --labels (svae_class_sums_update's limi
 INFER_STACK_FORMATS = (".npy", ".mrcs")
 INFER_MAX_CLUSTERS = min(INFER_MAX_CLASSES, 1024)   # classes of --cluster (include/svae_cluster.h's limit on k)
 INFER_MAX_RESTARTS = 16
+INFER_FRC_MAX_CLASSES = INFER_MAX_CLASSES // 2      # --frc keeps two half-set sums per class
+INFER_FRC_MAX_BOX = 1024    # include/svae_frc.h's limit on n and m
+FRC_THRESHOLDS = (("resolution_0143", 0.143), ("resolution_05", 0.5))
 
 
 def infer_arguments(argv=None):
@@ -86,8 +90,29 @@ def infer_arguments(argv=None):
                    "of lowest inertia is kept, the first of equals" % INFER_MAX_RESTARTS)
     p.add_argument("--cluster_seed", type=int, default=None, metavar="S", help="seed of the generator the k-means++ uniforms come "
                    "from (default --seed)")
+    p.add_argument("--frc", action="store_true", help="with --class_averages: also accumulate each class over two disjoint halves "
+                   "(image i of the split in half i & 1) and add their sums, the Fourier ring correlation of the two half averages, "
+                   "the resolution at the 0.143 and 0.5 thresholds and the full average filtered by sqrt(2 FRC / (1 + FRC)).  One "
+                   "model aligns both halves, so the figure is optimistic")
+    p.add_argument("--frc_mask_radius", type=float, default=None, metavar="PX", help="with --frc: radius of the soft circular mask "
+                   "put on both half averages before the transform (default max(min(rows, cols)/2 - edge, 1): a convention, not a "
+                   "tuned value); 0 = no mask")
+    p.add_argument("--frc_mask_edge", type=float, default=None, metavar="PX", help="with --frc: width of the mask's raised-cosine "
+                   "edge, PX > 0 (default 3, a convention too)")
     args = p.parse_args(argv)
     args.train_argv = train_argv
+    if not args.frc:
+        for name in ("frc_mask_radius", "frc_mask_edge"):
+            if vars(args)[name] is not None:
+                p.error("--%s needs --frc" % name)
+    else:
+        if args.class_averages is None:
+            p.error("--frc needs --class_averages")
+        if args.frc_mask_radius is not None and not 0 <= args.frc_mask_radius < float("inf"):
+            p.error("--frc_mask_radius must be a finite number >= 0 (got %r)" % args.frc_mask_radius)
+        args.frc_mask_edge = 3.0 if args.frc_mask_edge is None else args.frc_mask_edge
+        if not 0 < args.frc_mask_edge < float("inf"):
+            p.error("--frc_mask_edge must be a finite number > 0 (got %r)" % args.frc_mask_edge)
     if args.cluster is None:
         for name in ("cluster_out", "cluster_labels", "cluster_iters", "cluster_restarts", "cluster_seed"):
             if vars(args)[name] is not None:
@@ -160,7 +185,15 @@ def infer_arguments(argv=None):
             args.label_array = read_labels(args.labels)
         except ValueError as e:
             p.error(str(e))
+        if args.frc and args.label_array.size and args.label_array.max() + 1 > INFER_FRC_MAX_CLASSES:
+            p.error("--frc keeps two sums per class: at most %d classes (--labels has %d)"
+                    % (INFER_FRC_MAX_CLASSES, args.label_array.max() + 1))
     return args
+
+
+def frc_mask_radius(args, n, m):
+    """--frc_mask_radius, or its default for an n x m box: max(min(n, m)/2 - edge, 1)."""
+    return max(min(n, m) / 2.0 - args.frc_mask_edge, 1.0) if args.frc_mask_radius is None else float(args.frc_mask_radius)
 
 
 def read_labels(path):
@@ -332,6 +365,8 @@ def check_request(args, facts):
             _refuse("--cluster: this state is from before the run's z_delay ended (z_scale = 0): every content latent is 0")
         if args.cluster > images:
             _refuse("--cluster {} exceeds the {} images of the {} split".format(args.cluster, images, facts.split))
+    if args.frc and max(facts.n, facts.m) > INFER_FRC_MAX_BOX:
+        _refuse("--frc takes boxes of at most {0}x{0} pixels, these images are {1}x{2}".format(INFER_FRC_MAX_BOX, facts.n, facts.m))
     if args.label_array is not None and args.label_array.shape[0] != images:
         _refuse("--labels has {} entries, the {} split has {} images".format(args.label_array.shape[0], facts.split, images))
     for k in ("aligned", "recon"):
@@ -366,7 +401,8 @@ def upload_split(cfg, split, device):
 class Accumulators(object):
     """What the image outputs accumulate over the minibatches: the pinned host stacks of --aligned / --recon (filled by
     non-blocking copies), the class sums of --class_averages with their labels on the device, and under --ctf_correct the
-    uploaded table rows of the split and, for wiener, the pair (class sums of the aligned H*y, class sums of H^2)."""
+    uploaded table rows of the split and, for wiener, the pair (class sums of the aligned H*y, class sums of H^2).  Under --frc
+    also the half-set sums: class k's images of even dataset index in row 2k, of odd index in row 2k + 1."""
 
     def __init__(self, args, facts, cfg, device):
         images, n, m, channels = facts.images, facts.n, facts.m, facts.channels
@@ -375,7 +411,7 @@ class Accumulators(object):
         self.stacks = {k: torch.empty(images, n * m * channels, dtype=torch.float32, pin_memory=True)
                        for k in ("aligned", "recon") if vars(args)[k] is not None}
         self.labels = args.label_array              # host; under --cluster both arrive after the scoring walk
-        self.sums = self.label_d = self.table_d = self.wiener = self.ctf_scale = None
+        self.sums = self.label_d = self.table_d = self.wiener = self.ctf_scale = self.halves = self.frc = None
         if args.class_averages is not None:
             if args.cluster is not None:
                 n_classes = args.cluster
@@ -385,6 +421,8 @@ class Accumulators(object):
                 n_classes = max(int(self.labels.max()) + 1, 1) if images else 1
                 self.label_d = torch.from_numpy(self.labels.astype(np.int32)).to(device)
             self.sums = ops.ClassSums(n_classes, n * m, channels, device)
+            if args.frc:
+                self.halves = ops.ClassSums(2 * n_classes, n * m, channels, device)
         if self.correct is not None:                # each image through its own transfer function before it is aligned
             table = cfg["ctf_params_" + facts.split]
             self.table_d = torch.from_numpy(np.ascontiguousarray(table[:images], dtype=np.float64)).to(device)
@@ -395,6 +433,12 @@ class Accumulators(object):
 
     def _align(self, y, per_image, q_mu):
         return E.align_minibatch(y, self.n, self.m, per_image, q_mu, self.rotate, self.translate, self.pose, self.interp)
+
+    def _half_labels(self, lo, hi):
+        """label_d[lo:hi] with class k split by the parity of the dataset index: 2k + (i & 1); -1 stays -1."""
+        label = self.label_d[lo:hi]
+        parity = torch.arange(lo, hi, dtype=torch.int32, device=label.device) & 1
+        return torch.where(label >= 0, 2 * label + parity, label).contiguous()
 
     def align_and_update(self, lo, y, per_image, q_mu, labelled):
         """The minibatch y = images [lo, lo + B) brought into the canonical frame, copied into the aligned stack when there is
@@ -408,8 +452,12 @@ class Accumulators(object):
             g, g_cover = self._align(g, per_image, q_mu)
             self.wiener[0].update(g, g_cover, self.label_d[lo:hi])
             self.wiener[1].update(self.table_d[lo:hi], self.label_d[lo:hi])
+            if self.halves is not None:             # the halves of what the Wiener average divides: the aligned H y
+                self.halves.update(g, g_cover, self._half_labels(lo, hi))
         if labelled:
             self.sums.update(aligned, cover, self.label_d[lo:hi])
+            if self.halves is not None and self.wiener is None:
+                self.halves.update(aligned, cover, self._half_labels(lo, hi))
         return aligned
 
     def keep(self, name, lo, images):
@@ -466,6 +514,32 @@ def cluster_walk(args, model, split, acc, rows, lay):
     return fit, centres
 
 
+def frc_finish(args, facts, acc):
+    """--frc, once after the walks and on the device: the two half planes of every (class, channel) -- half_sum / half_count
+    where the count is positive and 0 elsewhere, under --ctf_correct wiener half_sum itself (a positive weight shared by both
+    halves leaves a ring correlation nearly unchanged, and the numerators are the phase-corrected quantity) -- through ops.frc
+    under the mask, and the full average (sum / count, or the Wiener average) through ops.frc_filter with elbo.frc_weight.
+    Nothing is read back; class_arrays takes acc.frc from here."""
+    n, m, channels, K = facts.n, facts.m, facts.channels, acc.sums.n_classes
+    h_sum, h_count = acc.halves.result()
+    h_sum, h_count = h_sum.view(K, 2, n * m, channels), h_count.view(K, 2, n * m, 1)
+    total, count = acc.sums.result()
+    count = count.view(K, n * m, 1)
+    if acc.wiener is not None:
+        planes = h_sum
+        full = ops.wiener_finish(acc.wiener[0].result()[0], acc.wiener[1].result(), args.wiener_lambda, n, m).double()
+        full = full.view(K, 1, n * m)
+    else:
+        planes = torch.where(h_count > 0, h_sum / h_count, torch.zeros_like(h_sum))
+        full = torch.where(count > 0, total / count, torch.zeros_like(total)).permute(0, 2, 1)
+    halves = planes.permute(1, 0, 3, 2).reshape(2, K * channels, n, m)     # (half, class * channel, n, m)
+    sums, frc, ring_count = ops.frc(halves[0], halves[1], n, m, frc_mask_radius(args, n, m), args.frc_mask_edge)
+    weight = E.frc_weight(frc)
+    filtered = ops.frc_filter(full.reshape(K * channels, n, m), weight, n, m)
+    acc.frc = {"frc_sums": sums.view(K, channels, -1, 3), "frc": frc.view(K, channels, -1), "ring_count": ring_count,
+               "frc_weight": weight.view(K, channels, -1), "average_filtered": filtered.view(K, channels, n, m).permute(0, 2, 3, 1)}
+
+
 def collect(args, facts, lay, rows, acc, fit, centres):
     """The one transfer of the scores (and the one synchronisation, when stacks were filled) and what the files will hold:
     (the score file's arrays, the --cluster_out arrays or None, the host labels of the classes, the summary line)."""
@@ -482,6 +556,8 @@ def collect(args, facts, lay, rows, acc, fit, centres):
         meta.update(pose=args.pose, interp=args.interp, labels=args.labels, **want)
     if args.ctf_correct is not None:
         meta.update(ctf_correct=args.ctf_correct, wiener_lambda=args.wiener_lambda)
+    if args.frc:
+        meta.update(frc=True, frc_mask_radius=frc_mask_radius(args, facts.n, facts.m), frc_mask_edge=args.frc_mask_edge)
     found, labels = None, acc.labels
     if fit is not None:
         meta.update(pose=args.pose, cluster=args.cluster, cluster_out=args.cluster_out, cluster_labels=args.cluster_labels,
@@ -515,7 +591,31 @@ def class_arrays(args, facts, acc, labels):
         classes.update(wiener_sum=w_sum.cpu().numpy().reshape(sums.n_classes, n, m, 1), wiener_den=w_den.cpu().numpy(),
                        wiener_average=w_avg.cpu().numpy().reshape(sums.n_classes, n, m, 1),
                        wiener_lambda=np.float64(args.wiener_lambda))
+    if acc.frc is not None:
+        classes.update(frc_arrays(args, facts, acc, labels))
     return classes
+
+
+def frc_arrays(args, facts, acc, labels):
+    """The arrays --frc adds to the --class_averages file: the half-set sums, counts and members, what frc_finish left on the
+    device, and from the FRC curves on the host the resolution in pixels at both thresholds."""
+    n, m, K = facts.n, facts.m, acc.sums.n_classes
+    h_sum, h_count = (t.cpu().numpy() for t in acc.halves.result())
+    out = {k: np.ascontiguousarray(v.cpu().numpy()) for k, v in acc.frc.items()}
+    L, R, ring_frequency = E.ring_layout(n, m)
+    in_class = labels >= 0
+    members = np.bincount(2 * labels[in_class] + (np.arange(labels.shape[0])[in_class] & 1), minlength=2 * K)
+    out.update(half_sum=h_sum.reshape(K, 2, n, m, facts.channels), half_count=h_count.reshape(K, 2, n, m),
+               half_members=members.astype(np.int64).reshape(K, 2), ring_frequency=ring_frequency,
+               frc_mask=E.frc_mask_weights(n, m, frc_mask_radius(args, n, m), args.frc_mask_edge))
+    never = np.zeros((K, facts.channels, len(FRC_THRESHOLDS)), bool)
+    for j, (name, threshold) in enumerate(FRC_THRESHOLDS):
+        out[name] = np.empty((K, facts.channels), np.float64)
+        for k in range(K):
+            for c in range(facts.channels):
+                out[name][k, c], never[k, c, j] = E.frc_resolution(out["frc"][k, c], threshold, L)
+    out["frc_never_below"] = never
+    return out
 
 
 def write_outputs(args, facts, acc, arrays, found, labels):
@@ -542,6 +642,8 @@ def infer_main(args, parser_fn, build, positional=()):
     acc = Accumulators(args, facts, model.cfg, model.device)
     rows = score_walk(args, model, split, acc)
     fit, centres = cluster_walk(args, model, split, acc, rows, lay) if args.cluster is not None else (None, None)
+    if args.frc:
+        frc_finish(args, facts, acc)
     arrays, found, labels, summary = collect(args, facts, lay, rows, acc, fit, centres)
     write_outputs(args, facts, acc, arrays, found, labels)
     print(summary)

@@ -51,7 +51,8 @@ def _p(t):
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
                  for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES,
-                                             **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES}.items()}
+                                             **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES,
+                                             **_lib.FRC_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -773,6 +774,46 @@ def wiener_finish(sum, den, lam, n, m):
     ws_bytes = _lib.lib().svae_wiener_finish_workspace_bytes(n_classes, n, m)
     ws = _buf(sum.device, ws_bytes, "ctfcorr") if ws_bytes else None
     _call("svae_wiener_finish", sum.device, sum.contiguous(), den.contiguous(), float(lam), n_classes, n, m, out, ws, ws_bytes)
+    return out
+
+
+def frc(a, b, n, m, mask_radius=0.0, mask_edge=0.0):
+    """The Fourier ring correlation of each pair of planes (svae_frc, include/svae_frc.h): a, b (planes, n*m) or (planes, n, m)
+    float64 on the device, under the soft circular mask (mask_radius 0 = none).  Returns (sums (planes, R, 3) = [num, pa, pb],
+    frc (planes, R), both float64, ring_count (R) int32) with R = min(n, m) // 2 + 1, on the device; nothing is read back."""
+    _require_hip(a, "a")
+    _require_hip(b, "b")
+    if a.dtype != torch.float64 or b.dtype != torch.float64:
+        raise RuntimeError("frc: a and b must be float64")
+    planes = a.size(0)
+    if a.numel() != planes * n * m or b.numel() != planes * n * m:
+        raise RuntimeError("frc: a %s / b %s do not hold %d planes of %dx%d each" % (tuple(a.shape), tuple(b.shape), planes, n, m))
+    R = min(n, m) // 2 + 1
+    sums = torch.empty(planes, R, 3, dtype=torch.float64, device=a.device)
+    out = torch.empty(planes, R, dtype=torch.float64, device=a.device)
+    ring_count = torch.empty(R, dtype=torch.int32, device=a.device)
+    ws_bytes = _lib.lib().svae_frc_workspace_bytes(planes, n, m)        # 0 while the planes fit the LDS (up to 71 x 71)
+    ws = _buf(a.device, ws_bytes, "frc") if ws_bytes else None
+    _call("svae_frc", a.device, a.contiguous(), b.contiguous(), planes, n, m, float(mask_radius), float(mask_edge), sums, out,
+          ring_count, ws, ws_bytes)
+    return sums, out, ring_count
+
+
+def frc_filter(x, weight, n, m):
+    """Each plane filtered by its per-ring weights, Re IDFT( weight[p, ring] DFT(x[p]) ) (svae_frc_filter): x (planes, n*m) or
+    (planes, n, m) and weight (planes, R) float64 on the device.  Returns (planes, n, m) float32."""
+    _require_hip(x, "x")
+    _require_hip(weight, "weight")
+    if x.dtype != torch.float64 or weight.dtype != torch.float64:
+        raise RuntimeError("frc_filter: x and weight must be float64")
+    planes, R = x.size(0), min(n, m) // 2 + 1
+    if x.numel() != planes * n * m or weight.numel() != planes * R:
+        raise RuntimeError("frc_filter: x %s / weight %s do not hold %d planes of %dx%d and their %d rings"
+                           % (tuple(x.shape), tuple(weight.shape), planes, n, m, R))
+    out = torch.empty(planes, n, m, dtype=torch.float32, device=x.device)
+    ws_bytes = _lib.lib().svae_frc_filter_workspace_bytes(planes, n, m)
+    ws = _buf(x.device, ws_bytes, "frc") if ws_bytes else None
+    _call("svae_frc_filter", x.device, x.contiguous(), weight.contiguous(), planes, n, m, out, ws, ws_bytes)
     return out
 
 
