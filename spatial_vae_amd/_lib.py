@@ -174,6 +174,15 @@ FRC_SIGNATURES = {
 }
 
 
+# ---- include/svae_refine.h: the reference-based pose search, a seventh header with a table of its own ----
+# Same rules (tests/test_refine_cpu.py holds these rows to that header's prototypes).  The header adds no constant: `interp` takes
+# the values of ALIGN_INTERP.
+REFINE_SIGNATURES = {
+    "svae_pose_search_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "svae_pose_search": (cint, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f64, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -197,7 +206,7 @@ def lib():
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
     for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES,
-                                      **CLUSTER_SIGNATURES, **FRC_SIGNATURES}.items():
+                                      **CLUSTER_SIGNATURES, **FRC_SIGNATURES, **REFINE_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

@@ -22,45 +22,28 @@ __device__ __forceinline__ void align_cubic_weights(double t, double w[4]) {
     w[3] = (t3 - t2) / 2.0;
 }
 
-// One thread per output element (b, jy, jx, c); the thread of channel 0 also writes the pixel's coverage.
+// The canonical-frame value of output pixel (jy, jx), channel ch, of the image `img` (h, w, C) at the pose (c = cos theta,
+// s = sin theta, dx0, dx1), in double: the header's geometry, coverage, clamping and interpolation, before the one rounding to
+// float.  *covered is false (and the value 0) where the observed image does not cover the pixel; a NaN pose lands there too,
+// every comparison being false.  align_images_kernel and refine.h's pose search share it.
 template <bool CUBIC>
-__global__ void align_images_kernel(const float* __restrict__ y, const float* __restrict__ theta, const float* __restrict__ dx,
-                                    float* __restrict__ out, uint8_t* __restrict__ cover, AlignGeo g) {
+__device__ __forceinline__ double align_sample(const float* __restrict__ img, double c, double s, double dx0, double dx1, int jy,
+                                               int jx, int ch, int h, int w, int C, bool* covered_out) {
 #pragma clang fp contract(off)
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long per = (long)g.rows * g.cols * g.C;
-    if (t >= per * g.B) return;
-    const int b = (int)(t / per);
-    const int rem = (int)(t - (long)b * per);
-    const int ch = rem % g.C;
-    const int pix = rem / g.C;
-    const int jx = pix % g.cols, jy = pix / g.cols;
-    const int w = g.cols, h = g.rows;
     const double a = (double)(w - 1) / 2.0, bq = (double)(h - 1) / 2.0;
-    double c = 1.0, s = 0.0;
-    if (theta) {
-        const double th = (double)theta[b];
-        c = cos(th);
-        s = sin(th);
-    }
-    const double dx0 = dx ? (double)dx[2 * b] : 0.0, dx1 = dx ? (double)dx[2 * b + 1] : 0.0;
     const double X = (double)jx - a, Y = bq - (double)jy;
     const double U = X - a * dx0, V = Y - bq * dx1;
     const double SX = c * U + s * (a / bq) * V;
     const double SY = -s * (bq / a) * U + c * V;
     double fx = SX + a, fy = bq - SY;
     const bool covered = fx >= -1e-6 && fx <= (double)(w - 1) + 1e-6 && fy >= -1e-6 && fy <= (double)(h - 1) + 1e-6;
-    if (cover && ch == 0) cover[(long)b * h * w + pix] = covered ? 1 : 0;
-    if (!covered) {  // a NaN pose lands here too: every comparison above is false
-        out[t] = 0.0f;
-        return;
-    }
+    *covered_out = covered;
+    if (!covered) return 0.0;
     fx = fmin(fmax(fx, 0.0), (double)(w - 1));
     fy = fmin(fmax(fy, 0.0), (double)(h - 1));
     const int i0 = min((int)floor(fx), w - 2), j0 = min((int)floor(fy), h - 2);
     const double tx = fx - (double)i0, ty = fy - (double)j0;
-    const float* img = y + (long)b * per;
-    auto sample = [&](int yy, int xx) -> double { return (double)img[((long)yy * w + xx) * g.C + ch]; };
+    auto sample = [&](int yy, int xx) -> double { return (double)img[((long)yy * w + xx) * C + ch]; };
     double v;
     if (CUBIC) {
         double wx[4], wy[4];
@@ -82,7 +65,33 @@ __global__ void align_images_kernel(const float* __restrict__ y, const float* __
         const double r1 = (1.0 - tx) * sample(j0 + 1, i0) + tx * sample(j0 + 1, i0 + 1);
         v = (1.0 - ty) * r0 + ty * r1;
     }
-    out[t] = (float)v;
+    return v;
+}
+
+// One thread per output element (b, jy, jx, c); the thread of channel 0 also writes the pixel's coverage.
+template <bool CUBIC>
+__global__ void align_images_kernel(const float* __restrict__ y, const float* __restrict__ theta, const float* __restrict__ dx,
+                                    float* __restrict__ out, uint8_t* __restrict__ cover, AlignGeo g) {
+#pragma clang fp contract(off)
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long per = (long)g.rows * g.cols * g.C;
+    if (t >= per * g.B) return;
+    const int b = (int)(t / per);
+    const int rem = (int)(t - (long)b * per);
+    const int ch = rem % g.C;
+    const int pix = rem / g.C;
+    const int jx = pix % g.cols, jy = pix / g.cols;
+    double c = 1.0, s = 0.0;
+    if (theta) {
+        const double th = (double)theta[b];
+        c = cos(th);
+        s = sin(th);
+    }
+    const double dx0 = dx ? (double)dx[2 * b] : 0.0, dx1 = dx ? (double)dx[2 * b + 1] : 0.0;
+    bool covered;
+    const double v = align_sample<CUBIC>(y + (long)b * per, c, s, dx0, dx1, jy, jx, ch, g.rows, g.cols, g.C, &covered);
+    if (cover && ch == 0) cover[(long)b * g.rows * g.cols + pix] = covered ? 1 : 0;
+    out[t] = covered ? (float)v : 0.0f;
 }
 
 // One thread per (class k, pixel j): walks the call's B labels in index order and adds the images of its class into

@@ -18,6 +18,7 @@
 #include "../../include/svae_ctfcorr.h"
 #include "../../include/svae_cluster.h"
 #include "../../include/svae_frc.h"
+#include "../../include/svae_refine.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
@@ -26,6 +27,7 @@
 #include "align.h"
 #include "ctfcorr.h"
 #include "frc.h"
+#include "refine.h"
 #include "cluster.h"
 #include "encoder.h"
 #include "split.h"
@@ -1912,6 +1914,62 @@ int svae_frc_filter(const double* x, const double* weight, int32_t planes, int32
         return fail(SVAE_E_INVALID, "svae_frc_filter: x and weight must not overlap out");
     return dft_launch("svae_frc_filter", frc_filter_kernel<false>, frc_filter_kernel<true>, planes, n, m, ws,
                       static_cast<hipStream_t>(stream), x, weight, (int)planes, (int)n, (int)m, out);
+}
+
+// ---- reference-based pose search (include/svae_refine.h) ----
+namespace {
+// doubles one workgroup keeps: the resampled plane and the image's score volume (+ 8 for the block sums in the LDS form)
+size_t refine_doubles(int rows, int cols, int C, int A, int S) {
+    return (size_t)rows * cols * C + (size_t)(2 * A + 1) * (2 * S + 1) * (2 * S + 1);
+}
+bool refine_sizes_ok(int B, int rows, int cols, int C, int A, int S) {
+    return B >= 1 && rows >= 2 && rows <= 1024 && cols >= 2 && cols <= 1024 && C >= 1 && C <= SVAE_MAX_OUT && A >= 0 && A <= 32 &&
+           S >= 0 && S <= 8;
+}
+bool refine_in_lds(int rows, int cols, int C, int A, int S) { return (refine_doubles(rows, cols, C, A, S) + 8) * sizeof(double) <= CTF_LDS_MAX; }
+// the slice of one workgroup in the workspace form, in doubles: a multiple of 256 bytes
+size_t refine_slice(int rows, int cols, int C, int A, int S) { return (refine_doubles(rows, cols, C, A, S) + 31) & ~size_t(31); }
+}  // namespace
+
+size_t svae_pose_search_workspace_bytes(int32_t B, int32_t rows, int32_t cols, int32_t C, int32_t A, int32_t S) {
+    if (!refine_sizes_ok(B, rows, cols, C, A, S) || refine_in_lds(rows, cols, C, A, S)) return 0;
+    return (size_t)dft_groups(B) * refine_slice(rows, cols, C, A, S) * sizeof(double);
+}
+
+int svae_pose_search(const float* y, const double* ref, const double* weight, const int32_t* ref_index, const float* pose_in,
+                     int32_t B, int32_t n_ref, int32_t rows, int32_t cols, int32_t C, int32_t A, double step, int32_t S,
+                     int32_t interp, float* pose_out, double* score, int32_t* offset, double* scores, void* ws, size_t ws_bytes,
+                     svae_stream_t stream) {
+    if (!refine_sizes_ok(B, rows, cols, C, A, S) || n_ref < 1)
+        return fail(SVAE_E_INVALID, "svae_pose_search: bad sizes B=%d n_ref=%d rows=%d cols=%d C=%d A=%d S=%d (rows, cols in 2..1024, "
+                    "C in 1..%d, A in 0..32, S in 0..8)", B, n_ref, rows, cols, C, A, S, SVAE_MAX_OUT);
+    if ((long)B * rows * cols * C > 0x7fffffffL || (long)n_ref * rows * cols * C > 0x7fffffffL)
+        return fail(SVAE_E_INVALID, "svae_pose_search: %d images or %d references of %d x %d x %d are too many", B, n_ref, rows, cols, C);
+    if (A > 0 && (!(step > 0.0) || isinf(step))) return fail(SVAE_E_INVALID, "svae_pose_search: step must be finite and > 0 where A > 0");
+    if (interp != SVAE_ALIGN_BILINEAR && interp != SVAE_ALIGN_BICUBIC)
+        return fail(SVAE_E_INVALID, "svae_pose_search: unknown interpolation %d", interp);
+    if (!y || !ref || !ref_index || !pose_in || !pose_out || !score || !offset)
+        return fail(SVAE_E_INVALID, "svae_pose_search: null y, ref, ref_index, pose_in, pose_out, score or offset");
+    const bool scratch = !refine_in_lds(rows, cols, C, A, S);
+    const size_t need = svae_pose_search_workspace_bytes(B, rows, cols, C, A, S);
+    if (scratch && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255)))
+        return fail(SVAE_E_INVALID, "svae_pose_search: %d x %d x %d images with A=%d, S=%d need a workspace of %zu bytes, 256-byte "
+                    "aligned (got %zu)", rows, cols, C, A, S, need, ws_bytes);
+    using K = decltype(&pose_search_kernel<false, false>);
+    const bool cubic = interp == SVAE_ALIGN_BICUBIC;
+    K kernel = scratch ? (cubic ? pose_search_kernel<true, true> : pose_search_kernel<false, true>)
+                       : (cubic ? pose_search_kernel<true, false> : pose_search_kernel<false, false>);
+    const size_t lds = (scratch ? 8 : refine_doubles(rows, cols, C, A, S) + 8) * sizeof(double);
+    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return fail(SVAE_E_LAUNCH, "svae_pose_search: cannot reserve %zu bytes of LDS", lds);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const RefineGeo g{B, n_ref, rows, cols, C, A, S, A > 0 ? step : 0.0};
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(kernel, dim3(scratch ? dft_groups(B) : B), dim3(256), lds, st, y, ref, weight, reinterpret_cast<const int*>(ref_index),
+                       pose_in, g, pose_out, score, reinterpret_cast<int*>(offset), scores, static_cast<double*>(scratch ? ws : nullptr),
+                       (long)refine_slice(rows, cols, C, A, S));
+    return launch_status("svae_pose_search");
 }
 
 // ---- k-means over the content latents (include/svae_cluster.h) ----

@@ -268,11 +268,46 @@ def align_minibatch(y, rows, cols, per_image, q_mu, rotate, translate, pose="iw"
     """The minibatch's observed images brought into the model's canonical frame (ops.align_images) at the pose estimate
     `pose` (POSES) taken from score_minibatch's "per_image" and "q_mu": device slices, nothing is read back.  Returns (aligned,
     shaped like y; cover (B, rows*cols) uint8).  A model with neither rotation nor translation gets its images back."""
+    return align_at(y, rows, cols, initial_pose(per_image, q_mu, rotate, translate, pose), rotate, translate, interp)
+
+
+def initial_pose(per_image, q_mu, rotate, translate, pose="iw"):
+    """The (B, 3) fp32 tensor theta, dx0, dx1 of the estimate `pose` (POSES), in the decoder's units, out of score_minibatch's
+    "per_image" and "q_mu": a coordinate the model does not infer is 0.  The one statement of what aligns an image before any
+    refinement; device slices, nothing is read back."""
     lay = row_layout(rotate, translate, q_mu.size(1))
     lat = _pose_rows(per_image, q_mu, pose, lay)
-    theta = lat[:, 0].contiguous() if rotate else None
-    dx = lat[:, lay.dx].contiguous() if translate else None
+    out = torch.zeros(lat.size(0), 3, dtype=torch.float32, device=lat.device)
+    if rotate:
+        out[:, 0] = lat[:, 0]
+    if translate:
+        out[:, 1:] = lat[:, lay.dx]
+    return out
+
+
+@torch.no_grad()
+def align_at(y, rows, cols, pose3, rotate=True, translate=True, interp="bicubic"):
+    """ops.align_images at the (B, 3) poses of initial_pose / refine_poses; a coordinate the model does not infer is not handed
+    over (NULL: the exact identity).  Returns (aligned, cover)."""
+    theta = pose3[:, 0].contiguous() if rotate else None
+    dx = pose3[:, 1:].contiguous() if translate else None
     return ops.align_images(y, theta, dx, rows, cols, interp)
+
+
+def refine_mask(n, m, S):
+    """The weight the pose search puts on the reference of an n x m box searched over shifts of at most S pixels, (n, m) float64
+    on the host: frc_mask_weights with edge = 3 and radius = max(min(n, m)/2 - 3 - S, 1), so that no shift of the search moves
+    a weighted pixel across the border.  A convention, not a tuned value."""
+    return frc_mask_weights(n, m, max(min(n, m) / 2.0 - 3.0 - S, 1.0), 3.0)
+
+
+@torch.no_grad()
+def refine_poses(y, rows, cols, ref, weight, ref_index, pose3, angles, step, shift, interp="bicubic"):
+    """One round of reference-based refinement for one minibatch (ops.pose_search): around each image's pose3 row, 2 * angles
+    + 1 rotations `step` radians apart and the integer shifts up to `shift` pixels, scored by the weighted correlation of the
+    re-aligned image with ref[ref_index[b]].  Returns ops.PoseSearch(pose (B, 3), score (B), offset (B, 4), None) on the device;
+    an image with ref_index -1 or an all-zero reference keeps its pose."""
+    return ops.pose_search(y, ref, weight, ref_index, pose3, rows, cols, angles, step, shift, interp)
 
 
 def content_latents(per_image, q_mu, rotate, translate, pose="iw"):

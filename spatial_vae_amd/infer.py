@@ -2,12 +2,14 @@
 
 Its own command line (infer_arguments: every refusal that needs no data, made before the kernel library is loaded), its file
 writers, and infer_main: a short sequence of stages -- load the model, check the request against the split, allocate the
-accumulators, walk the minibatches scoring (and aligning) them, cluster, finish the half-set correlation (--frc), collect and
-write.  The device work is elbo.py's (score_minibatch, align_minibatch, reconstruct_unposed, cluster_latents, frc_weight) and
-ops.py's.
+accumulators, walk the minibatches scoring (and aligning) them, cluster, refine the poses against the class averages (--refine),
+finish the half-set correlation (--frc), collect and
+write.  The device work is elbo.py's (score_minibatch, align_minibatch, reconstruct_unposed, cluster_latents, refine_poses,
+frc_weight) and ops.py's.
 """
 import collections
 import json
+import math
 import os
 import sys
 
@@ -28,6 +30,9 @@ INFER_MAX_RESTARTS = 16
 INFER_FRC_MAX_CLASSES = INFER_MAX_CLASSES // 2      # --frc keeps two half-set sums per class
 INFER_FRC_MAX_BOX = 1024    # include/svae_frc.h's limit on n and m
 FRC_THRESHOLDS = (("resolution_0143", 0.143), ("resolution_05", 0.5))
+INFER_MAX_REFINE_ROUNDS = 10
+INFER_MAX_REFINE_ANGLES = 32    # include/svae_refine.h's limits on A and S
+INFER_MAX_REFINE_SHIFT = 8
 
 
 def infer_arguments(argv=None):
@@ -99,8 +104,39 @@ def infer_arguments(argv=None):
                    "tuned value); 0 = no mask")
     p.add_argument("--frc_mask_edge", type=float, default=None, metavar="PX", help="with --frc: width of the mask's raised-cosine "
                    "edge, PX > 0 (default 3, a convention too)")
+    p.add_argument("--refine", type=int, default=None, metavar="R", help="with --class_averages: R rounds (1..%d) of reference-based "
+                   "alignment.  Each round takes the class averages as they stand as references, searches a small neighbourhood of "
+                   "rotations and shifts around every image's pose for the best weighted correlation with the average of its class, "
+                   "and accumulates the averages again at the new poses.  With --frc each half is refined against its own half "
+                   "average only.  The file keeps the first averages as average_unrefined" % INFER_MAX_REFINE_ROUNDS)
+    p.add_argument("--refine_angles", type=int, default=None, metavar="A", help="with --refine: rotations searched on each side of "
+                   "the current one, 0..%d (default 5)" % INFER_MAX_REFINE_ANGLES)
+    p.add_argument("--refine_step", type=float, default=None, metavar="DEG", help="with --refine: their spacing in degrees, DEG > 0 "
+                   "(default 2.0)")
+    p.add_argument("--refine_shift", type=int, default=None, metavar="S", help="with --refine: shifts searched, whole pixels up to S "
+                   "on both axes, 0..%d (default 2)" % INFER_MAX_REFINE_SHIFT)
     args = p.parse_args(argv)
     args.train_argv = train_argv
+    if args.refine is None:
+        for name in ("refine_angles", "refine_step", "refine_shift"):
+            if vars(args)[name] is not None:
+                p.error("--%s needs --refine" % name)
+    else:
+        if not 1 <= args.refine <= INFER_MAX_REFINE_ROUNDS:
+            p.error("--refine must be in [1, %d] (got %d)" % (INFER_MAX_REFINE_ROUNDS, args.refine))
+        if args.class_averages is None:
+            p.error("--refine needs --class_averages")
+        if args.ctf_correct == "wiener":
+            p.error("--refine does not take --ctf_correct wiener: the half references would need half denominators")
+        args.refine_angles = 5 if args.refine_angles is None else args.refine_angles
+        args.refine_step = 2.0 if args.refine_step is None else args.refine_step
+        args.refine_shift = 2 if args.refine_shift is None else args.refine_shift
+        if not 0 <= args.refine_angles <= INFER_MAX_REFINE_ANGLES:
+            p.error("--refine_angles must be in [0, %d] (got %d)" % (INFER_MAX_REFINE_ANGLES, args.refine_angles))
+        if not 0 < args.refine_step < float("inf"):
+            p.error("--refine_step must be a finite number > 0 (got %r)" % args.refine_step)
+        if not 0 <= args.refine_shift <= INFER_MAX_REFINE_SHIFT:
+            p.error("--refine_shift must be in [0, %d] (got %d)" % (INFER_MAX_REFINE_SHIFT, args.refine_shift))
     if not args.frc:
         for name in ("frc_mask_radius", "frc_mask_edge"):
             if vars(args)[name] is not None:
@@ -365,6 +401,11 @@ def check_request(args, facts):
             _refuse("--cluster: this state is from before the run's z_delay ended (z_scale = 0): every content latent is 0")
         if args.cluster > images:
             _refuse("--cluster {} exceeds the {} images of the {} split".format(args.cluster, images, facts.split))
+    if args.refine is not None:
+        if not facts.rotate and not facts.translate:
+            _refuse("--refine searches rotations and shifts, and this model infers neither")
+        if max(facts.n, facts.m) > INFER_FRC_MAX_BOX:
+            _refuse("--refine takes boxes of at most {0}x{0} pixels, these images are {1}x{2}".format(INFER_FRC_MAX_BOX, facts.n, facts.m))
     if args.frc and max(facts.n, facts.m) > INFER_FRC_MAX_BOX:
         _refuse("--frc takes boxes of at most {0}x{0} pixels, these images are {1}x{2}".format(INFER_FRC_MAX_BOX, facts.n, facts.m))
     if args.label_array is not None and args.label_array.shape[0] != images:
@@ -412,6 +453,7 @@ class Accumulators(object):
                        for k in ("aligned", "recon") if vars(args)[k] is not None}
         self.labels = args.label_array              # host; under --cluster both arrive after the scoring walk
         self.sums = self.label_d = self.table_d = self.wiener = self.ctf_scale = self.halves = self.frc = None
+        self.refined = None                         # refine_walk's record, when --refine ran
         if args.class_averages is not None:
             if args.cluster is not None:
                 n_classes = args.cluster
@@ -445,7 +487,7 @@ class Accumulators(object):
         one; with `labelled` also its class-sum and Wiener updates under label_d.  The scoring walk and --cluster's second walk
         both make exactly these calls, in this order."""
         hi = lo + y.size(0)
-        seen = y if self.correct != "flip" else ops.ctf_apply(y, self.table_d[lo:hi], self.n, self.m, self.ctf_scale, "flip")
+        seen = self.seen(lo, y)
         aligned, cover = self._align(seen, per_image, q_mu)
         if labelled and self.wiener is not None:
             g = ops.ctf_apply(y, self.table_d[lo:hi], self.n, self.m, self.ctf_scale, "multiply")
@@ -458,6 +500,22 @@ class Accumulators(object):
             self.sums.update(aligned, cover, self.label_d[lo:hi])
             if self.halves is not None and self.wiener is None:
                 self.halves.update(aligned, cover, self._half_labels(lo, hi))
+        return aligned
+
+    def seen(self, lo, y):
+        """What is aligned of the minibatch y = images [lo, lo + B): the raw images, or under --ctf_correct flip the phase-flipped."""
+        if self.correct != "flip":
+            return y
+        return ops.ctf_apply(y, self.table_d[lo:lo + y.size(0)], self.n, self.m, self.ctf_scale, "flip")
+
+    def update_at(self, lo, seen, pose3):
+        """refine_walk's half of align_and_update: `seen` aligned at the poses pose3 (B, 3) and added to the class sums (and the
+        half-set sums) under label_d.  --refine excludes the Wiener sums."""
+        hi = lo + seen.size(0)
+        aligned, cover = E.align_at(seen, self.n, self.m, pose3, self.rotate, self.translate, self.interp)
+        self.sums.update(aligned, cover, self.label_d[lo:hi])
+        if self.halves is not None:
+            self.halves.update(aligned, cover, self._half_labels(lo, hi))
         return aligned
 
     def keep(self, name, lo, images):
@@ -514,6 +572,57 @@ def cluster_walk(args, model, split, acc, rows, lay):
     return fit, centres
 
 
+def class_means(sums):
+    """sum / count of a ClassSums where the count is positive and 0 elsewhere, (n_classes, N, C) float64 on the device."""
+    total, count = sums.result()
+    count = count.unsqueeze(2)
+    return torch.where(count > 0, total / count, torch.zeros_like(total))
+
+
+def refine_walk(args, facts, split, acc, rows, lay):
+    """--refine: R rounds of reference-based alignment on the device.  A round snapshots the references from the accumulators as
+    they stand -- sum / count per class, under --frc half_sum / half_count per (class, half), so that no image is ever compared
+    with an average that holds images of the other half --, zeroes the accumulators, and walks the minibatches in dataset order:
+    the image align_and_update would align is searched around its stored pose (elbo.refine_poses under elbo.refine_mask), the
+    new pose stored, the image aligned at it and the update calls made.  The last round fills --aligned again.  A coordinate
+    the model does not infer is not searched.  Nothing is read back between or inside rounds; acc.refined keeps what the files
+    report, the accumulators and (under --frc) the curves from before the first round among it."""
+    n, m, bs, device = facts.n, facts.m, args.minibatch_size, acc.device
+    A = args.refine_angles if facts.rotate else 0
+    S = args.refine_shift if facts.translate else 0
+    step = math.radians(args.refine_step)
+    per_image, q_mu, _ = split_rows(torch.cat(rows), lay)
+    pose = E.initial_pose(per_image, q_mu, facts.rotate, facts.translate, args.pose)
+    before = {"sum": acc.sums.sum.clone(), "count": acc.sums.count.clone()}
+    if args.frc:
+        frc_finish(args, facts, acc)
+        before["frc"] = acc.frc["frc"]
+    weight = torch.from_numpy(E.refine_mask(n, m, S).reshape(-1)).to(device)
+    source = acc.halves if args.frc else acc.sums
+    score = torch.zeros(facts.images, args.refine, dtype=torch.float64, device=device)
+    offset = torch.zeros(facts.images, args.refine, 4, dtype=torch.int32, device=device)
+    for r in range(args.refine):
+        ref = class_means(source)                   # a new tensor: the accumulators can be zeroed
+        for t in (acc.sums, acc.halves):
+            if t is not None:
+                t.sum.zero_()
+                t.count.zero_()
+        new_pose = torch.empty_like(pose)
+        for lo in range(0, facts.images, bs):
+            hi = min(lo + bs, facts.images)
+            seen = acc.seen(lo, split.data[lo:hi])
+            ref_index = acc._half_labels(lo, hi) if args.frc else acc.label_d[lo:hi].contiguous()
+            found = E.refine_poses(seen, n, m, ref, weight, ref_index, pose[lo:hi].contiguous(), A, step, S, acc.interp)
+            new_pose[lo:hi] = found.pose
+            score[lo:hi, r] = found.score
+            offset[lo:hi, r] = found.offset
+            aligned = acc.update_at(lo, seen, found.pose)
+            if r == args.refine - 1 and "aligned" in acc.stacks:
+                acc.keep("aligned", lo, aligned)
+        pose = new_pose
+    acc.refined = dict(before, pose=pose, score=score, offset=offset)
+
+
 def frc_finish(args, facts, acc):
     """--frc, once after the walks and on the device: the two half planes of every (class, channel) -- half_sum / half_count
     where the count is positive and 0 elsewhere, under --ctf_correct wiener half_sum itself (a positive weight shared by both
@@ -558,6 +667,10 @@ def collect(args, facts, lay, rows, acc, fit, centres):
         meta.update(ctf_correct=args.ctf_correct, wiener_lambda=args.wiener_lambda)
     if args.frc:
         meta.update(frc=True, frc_mask_radius=frc_mask_radius(args, facts.n, facts.m), frc_mask_edge=args.frc_mask_edge)
+    if acc.refined is not None:
+        meta.update(refine=args.refine, refine_angles=args.refine_angles, refine_step=args.refine_step, refine_shift=args.refine_shift)
+        arrays.update(pose_refined=acc.refined["pose"].cpu().numpy(), refine_score=acc.refined["score"].cpu().numpy(),
+                      refine_offset=acc.refined["offset"].cpu().numpy())
     found, labels = None, acc.labels
     if fit is not None:
         meta.update(pose=args.pose, cluster=args.cluster, cluster_out=args.cluster_out, cluster_labels=args.cluster_labels,
@@ -576,15 +689,25 @@ def collect(args, facts, lay, rows, acc, fit, centres):
     return arrays, found, labels, summary
 
 
+def _host_average(total, count, shape):
+    """(sum, count, average) on the host from the device accumulators: the average is sum / count in float64 where the count is
+    positive, 0 elsewhere, rounded to float32."""
+    total, count = total.cpu().numpy().reshape(shape), count.cpu().numpy().reshape(shape[:3])
+    average = np.divide(total, count[..., None], out=np.zeros_like(total), where=count[..., None] > 0).astype(np.float32)
+    return total, count, average
+
+
 def class_arrays(args, facts, acc, labels):
     """The arrays of --class_averages: sums, counts, averages and members per class; under --ctf_correct wiener also the Wiener
-    averages with their numerator and denominator (another lambda needs no second run)."""
+    averages with their numerator and denominator (another lambda needs no second run); under --refine those of the last round,
+    and average_unrefined from before the first."""
     n, m, sums = facts.n, facts.m, acc.sums
-    total, count = (t.cpu().numpy() for t in sums.result())
-    total, count = total.reshape(sums.n_classes, n, m, facts.channels), count.reshape(sums.n_classes, n, m)
-    average = np.divide(total, count[..., None], out=np.zeros_like(total), where=count[..., None] > 0).astype(np.float32)
+    shape = (sums.n_classes, n, m, facts.channels)
+    total, count, average = _host_average(*sums.result(), shape)
     members = np.bincount(labels[labels >= 0], minlength=sums.n_classes).astype(np.int64)
     classes = {"sum": total, "count": count, "average": average, "members": members}
+    if acc.refined is not None:
+        classes["average_unrefined"] = _host_average(acc.refined["sum"], acc.refined["count"], shape)[2]
     if acc.wiener is not None:
         w_sum, w_den = acc.wiener[0].result()[0], acc.wiener[1].result()
         w_avg = ops.wiener_finish(w_sum, w_den, args.wiener_lambda, n, m)
@@ -615,6 +738,11 @@ def frc_arrays(args, facts, acc, labels):
             for c in range(facts.channels):
                 out[name][k, c], never[k, c, j] = E.frc_resolution(out["frc"][k, c], threshold, L)
     out["frc_never_below"] = never
+    if acc.refined is not None:                     # what the file would have held without --refine
+        out["frc_unrefined"] = np.ascontiguousarray(acc.refined["frc"].cpu().numpy())
+        for name, threshold in FRC_THRESHOLDS:
+            out[name + "_unrefined"] = np.array([[E.frc_resolution(out["frc_unrefined"][k, c], threshold, L)[0]
+                                                  for c in range(facts.channels)] for k in range(K)], np.float64).reshape(K, facts.channels)
     return out
 
 
@@ -642,6 +770,8 @@ def infer_main(args, parser_fn, build, positional=()):
     acc = Accumulators(args, facts, model.cfg, model.device)
     rows = score_walk(args, model, split, acc)
     fit, centres = cluster_walk(args, model, split, acc, rows, lay) if args.cluster is not None else (None, None)
+    if args.refine is not None:
+        refine_walk(args, facts, split, acc, rows, lay)
     if args.frc:
         frc_finish(args, facts, acc)
     arrays, found, labels, summary = collect(args, facts, lay, rows, acc, fit, centres)

@@ -52,7 +52,7 @@ def _p(t):
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
                  for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES,
                                              **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES,
-                                             **_lib.FRC_SIGNATURES}.items()}
+                                             **_lib.FRC_SIGNATURES, **_lib.REFINE_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -815,6 +815,51 @@ def frc_filter(x, weight, n, m):
     ws = _buf(x.device, ws_bytes, "frc") if ws_bytes else None
     _call("svae_frc_filter", x.device, x.contiguous(), weight.contiguous(), planes, n, m, out, ws, ws_bytes)
     return out
+
+
+PoseSearch = namedtuple("PoseSearch", "pose score offset scores")
+
+
+def pose_search(y, ref, weight, ref_index, pose, rows, cols, angles, step, shift, interp="bicubic", return_scores=False):
+    """The pose of each image refined against its reference (svae_pose_search, include/svae_refine.h): 2 * angles + 1 rotations
+    `step` radians apart and the integer shifts of at most `shift` pixels around `pose` (B, 3) fp32 = theta, dx0, dx1 in the
+    decoder's units; the winner is the candidate whose canonical-frame image correlates best with ref[ref_index[b]] under
+    `weight`, moved by a parabola through its neighbours on each axis.  y (B, rows*cols[, C]) fp32, ref (n_ref, rows*cols[, C])
+    float64, weight (rows*cols) float64 or None, ref_index (B) int32, all on the device.  Returns PoseSearch(pose (B, 3) fp32,
+    score (B) float64, offset (B, 4) int32 = k, sx, sy, flags, scores (B, 2 angles + 1, 2 shift + 1, 2 shift + 1) float64 or
+    None) on the device; nothing is read back."""
+    for name, t in (("y", y), ("ref", ref), ("ref_index", ref_index), ("pose", pose)):
+        _require_hip(t, name)
+    if interp not in _lib.ALIGN_INTERP:
+        raise RuntimeError("pose_search: interp must be one of %s, got %r" % (sorted(_lib.ALIGN_INTERP), interp))
+    B, N = y.size(0), rows * cols
+    yc = _f32(y)
+    C = yc.numel() // (B * N) if B * N else 0
+    if C < 1 or C * B * N != yc.numel():
+        raise RuntimeError("pose_search: y %s does not hold %d images of %dx%d" % (tuple(y.shape), B, rows, cols))
+    if ref.dtype != torch.float64 or ref.numel() % (N * C) or not ref.numel():
+        raise RuntimeError("pose_search: ref %s (%s) must be float64 planes of %dx%dx%d" % (tuple(ref.shape), ref.dtype, rows, cols, C))
+    n_ref = ref.numel() // (N * C)
+    if weight is not None:
+        _require_hip(weight, "weight")
+        if weight.dtype != torch.float64 or weight.numel() != N:
+            raise RuntimeError("pose_search: weight must be %d float64 values, got %s (%s)" % (N, tuple(weight.shape), weight.dtype))
+        weight = weight.contiguous()
+    if ref_index.dtype != torch.int32 or ref_index.numel() != B:
+        raise RuntimeError("pose_search: ref_index must be (%d) int32" % B)
+    if pose.dtype != torch.float32 or tuple(pose.shape) != (B, 3):
+        raise RuntimeError("pose_search: pose must be (%d, 3) float32, got %s (%s)" % (B, tuple(pose.shape), pose.dtype))
+    A, S = int(angles), int(shift)
+    dev = y.device
+    out = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float64, device=dev)
+    offset = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, 2 * A + 1, 2 * S + 1, 2 * S + 1, dtype=torch.float64, device=dev) if return_scores and A >= 0 and S >= 0 else None
+    ws_bytes = _lib.lib().svae_pose_search_workspace_bytes(B, rows, cols, C, A, S)     # 0 while plane and volume fit the LDS
+    ws = _buf(dev, ws_bytes, "refine") if ws_bytes else None
+    _call("svae_pose_search", dev, yc, ref.contiguous(), weight, ref_index.contiguous(), pose.contiguous(), B, n_ref, rows, cols, C,
+          A, float(step), S, _lib.ALIGN_INTERP[interp], out, score, offset, scores, ws, ws_bytes)
+    return PoseSearch(out, score, offset, scores)
 
 
 KMeansFit = namedtuple("KMeansFit", "label centres members record seed_index")
