@@ -183,6 +183,15 @@ REFINE_SIGNATURES = {
 }
 
 
+# ---- include/svae_classify.h: multi-reference alignment, an eighth header with a table of its own ----
+# Same rules (tests/test_classify_cpu.py holds these rows to that header's prototypes).  The header adds no constant: `interp`
+# takes the values of ALIGN_INTERP.
+CLASSIFY_SIGNATURES = {
+    "svae_pose_classify_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32]),
+    "svae_pose_classify": (cint, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f64, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -206,7 +215,8 @@ def lib():
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
     for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES,
-                                      **CLUSTER_SIGNATURES, **FRC_SIGNATURES, **REFINE_SIGNATURES}.items():
+                                      **CLUSTER_SIGNATURES, **FRC_SIGNATURES, **REFINE_SIGNATURES,
+                                      **CLASSIFY_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

@@ -19,6 +19,7 @@
 #include "../../include/svae_cluster.h"
 #include "../../include/svae_frc.h"
 #include "../../include/svae_refine.h"
+#include "../../include/svae_classify.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
@@ -28,6 +29,7 @@
 #include "ctfcorr.h"
 #include "frc.h"
 #include "refine.h"
+#include "classify.h"
 #include "cluster.h"
 #include "encoder.h"
 #include "split.h"
@@ -1970,6 +1972,65 @@ int svae_pose_search(const float* y, const double* ref, const double* weight, co
                        pose_in, g, pose_out, score, reinterpret_cast<int*>(offset), scores, static_cast<double*>(scratch ? ws : nullptr),
                        (long)refine_slice(rows, cols, C, A, S));
     return launch_status("svae_pose_search");
+}
+
+// ---- multi-reference alignment (include/svae_classify.h) ----
+namespace {
+size_t roundup32(size_t v) { return (v + 31) & ~size_t(31); }
+bool classify_sizes_ok(int B, int n_ref, int M, int rows, int cols, int C) {
+    return refine_sizes_ok(B, rows, cols, C, 0, 0) && n_ref >= 1 && M >= 1 && M <= 4096 && (long)B * rows * cols * C <= 0x7fffffffL &&
+           (long)n_ref * rows * cols * C <= 0x7fffffffL && (long)B * M <= 0x7fffffffL;
+}
+// doubles one workgroup keeps: the resampled plane and the M running maxima (+ 8 for the block sums in the LDS form)
+size_t classify_doubles(int M, int rows, int cols, int C) { return (size_t)rows * cols * C + (size_t)M; }
+bool classify_in_lds(int M, int rows, int cols, int C) { return (classify_doubles(M, rows, cols, C) + 8) * sizeof(double) <= CTF_LDS_MAX; }
+}  // namespace
+
+size_t svae_pose_classify_workspace_bytes(int32_t B, int32_t n_ref, int32_t M, int32_t rows, int32_t cols, int32_t C) {
+    if (!classify_sizes_ok(B, n_ref, M, rows, cols, C)) return 0;
+    size_t doubles = roundup32((size_t)n_ref);
+    if (!classify_in_lds(M, rows, cols, C)) doubles += (size_t)dft_groups(B) * roundup32(classify_doubles(M, rows, cols, C));
+    return doubles * sizeof(double);
+}
+
+int svae_pose_classify(const float* y, const double* ref, const double* weight, const int32_t* cand, const float* pose_in,
+                       int32_t B, int32_t n_ref, int32_t M, int32_t rows, int32_t cols, int32_t C, int32_t A, double step,
+                       int32_t S, int32_t interp, int32_t* choice, int32_t* ref_chosen, double* cand_score, double* margin,
+                       void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (!refine_sizes_ok(B, rows, cols, C, A, S) || n_ref < 1 || M < 1 || M > 4096)
+        return fail(SVAE_E_INVALID, "svae_pose_classify: bad sizes B=%d n_ref=%d M=%d rows=%d cols=%d C=%d A=%d S=%d (M in 1..4096, rows, "
+                    "cols in 2..1024, C in 1..%d, A in 0..32, S in 0..8)", B, n_ref, M, rows, cols, C, A, S, SVAE_MAX_OUT);
+    if (!classify_sizes_ok(B, n_ref, M, rows, cols, C))
+        return fail(SVAE_E_INVALID, "svae_pose_classify: %d images or %d references of %d x %d x %d, or %d x %d candidates, are too many",
+                    B, n_ref, rows, cols, C, B, M);
+    if (A > 0 && (!(step > 0.0) || isinf(step))) return fail(SVAE_E_INVALID, "svae_pose_classify: step must be finite and > 0 where A > 0");
+    if (interp != SVAE_ALIGN_BILINEAR && interp != SVAE_ALIGN_BICUBIC)
+        return fail(SVAE_E_INVALID, "svae_pose_classify: unknown interpolation %d", interp);
+    if (!y || !ref || !cand || !pose_in || !choice || !ref_chosen || !cand_score)
+        return fail(SVAE_E_INVALID, "svae_pose_classify: null y, ref, cand, pose_in, choice, ref_chosen or cand_score");
+    const bool scratch = !classify_in_lds(M, rows, cols, C);
+    const size_t need = svae_pose_classify_workspace_bytes(B, n_ref, M, rows, cols, C);
+    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
+        return fail(SVAE_E_INVALID, "svae_pose_classify: %d references and %d x %d x %d images with M=%d need a workspace of %zu bytes, "
+                    "256-byte aligned (got %zu)", n_ref, rows, cols, C, M, need, ws_bytes);
+    using K = decltype(&pose_classify_kernel<false, false>);
+    const bool cubic = interp == SVAE_ALIGN_BICUBIC;
+    K kernel = scratch ? (cubic ? pose_classify_kernel<true, true> : pose_classify_kernel<false, true>)
+                       : (cubic ? pose_classify_kernel<true, false> : pose_classify_kernel<false, false>);
+    const size_t lds = (scratch ? 8 : classify_doubles(M, rows, cols, C) + 8) * sizeof(double);
+    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return fail(SVAE_E_LAUNCH, "svae_pose_classify: cannot reserve %zu bytes of LDS", lds);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ClassifyGeo g{B, n_ref, M, rows, cols, C, A, S, A > 0 ? step : 0.0};
+    double* norms = static_cast<double*>(ws);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(classify_norms_kernel, dim3(n_ref), dim3(256), 0, st, ref, weight, rows * cols * C, C, norms);
+    hipLaunchKernelGGL(kernel, dim3(scratch ? dft_groups(B) : B), dim3(256), lds, st, y, ref, weight, reinterpret_cast<const int*>(cand),
+                       pose_in, g, static_cast<const double*>(norms), reinterpret_cast<int*>(choice), reinterpret_cast<int*>(ref_chosen),
+                       cand_score, margin, scratch ? norms + roundup32((size_t)n_ref) : nullptr,
+                       (long)roundup32(classify_doubles(M, rows, cols, C)));
+    return launch_status("svae_pose_classify");
 }
 
 // ---- k-means over the content latents (include/svae_cluster.h) ----

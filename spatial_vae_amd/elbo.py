@@ -310,6 +310,17 @@ def refine_poses(y, rows, cols, ref, weight, ref_index, pose3, angles, step, shi
     return ops.pose_search(y, ref, weight, ref_index, pose3, rows, cols, angles, step, shift, interp)
 
 
+@torch.no_grad()
+def classify_poses(y, rows, cols, ref, weight, cand, pose3, angles, step, shift, interp="bicubic"):
+    """One round of multi-reference alignment for one minibatch: ops.pose_classify scores each image against the references its
+    row of cand (B, M) int32 names (-1 = an empty slot) over refine_poses' neighbourhood, and ops.pose_search then refines the
+    pose against the chosen reference alone: the winner and the parabolas stay the work of one kernel.  Returns
+    (ops.PoseClassify, ops.PoseSearch) on the device; an image with no live slot has choice and ref_chosen -1 and keeps its
+    pose."""
+    picked = ops.pose_classify(y, ref, weight, cand, pose3, rows, cols, angles, step, shift, interp)
+    return picked, ops.pose_search(y, ref, weight, picked.ref_chosen, pose3, rows, cols, angles, step, shift, interp)
+
+
 def content_latents(per_image, q_mu, rotate, translate, pose="iw"):
     """The content part (B, z_dim) of the same estimate: what reconstruct_unposed decodes."""
     lay = row_layout(rotate, translate, q_mu.size(1))

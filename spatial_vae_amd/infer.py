@@ -2,10 +2,11 @@
 
 Its own command line (infer_arguments: every refusal that needs no data, made before the kernel library is loaded), its file
 writers, and infer_main: a short sequence of stages -- load the model, check the request against the split, allocate the
-accumulators, walk the minibatches scoring (and aligning) them, cluster, refine the poses against the class averages (--refine),
+accumulators, walk the minibatches scoring (and aligning) them, cluster, refine the poses against the class averages (--refine;
+with --reassign also the classes),
 finish the half-set correlation (--frc), collect and
 write.  The device work is elbo.py's (score_minibatch, align_minibatch, reconstruct_unposed, cluster_latents, refine_poses,
-frc_weight) and ops.py's.
+classify_poses, frc_weight) and ops.py's.
 """
 import collections
 import json
@@ -33,6 +34,7 @@ FRC_THRESHOLDS = (("resolution_0143", 0.143), ("resolution_05", 0.5))
 INFER_MAX_REFINE_ROUNDS = 10
 INFER_MAX_REFINE_ANGLES = 32    # include/svae_refine.h's limits on A and S
 INFER_MAX_REFINE_SHIFT = 8
+INFER_MAX_REASSIGN_CLASSES = 4096   # include/svae_classify.h's limit on M (2K slots never arise: a half sees its own K averages)
 
 
 def infer_arguments(argv=None):
@@ -115,8 +117,21 @@ def infer_arguments(argv=None):
                    "(default 2.0)")
     p.add_argument("--refine_shift", type=int, default=None, metavar="S", help="with --refine: shifts searched, whole pixels up to S "
                    "on both axes, 0..%d (default 2)" % INFER_MAX_REFINE_SHIFT)
+    p.add_argument("--reassign", action="store_true", help="with --refine: multi-reference alignment.  Each round scores every "
+                   "labelled image against the average of EVERY class over the same neighbourhood of poses and moves it to the class "
+                   "it fits best, then refines its pose against that class; with --frc against the averages of its own half only.  "
+                   "A class that loses every member has an all-zero average from then on, which the search skips: it stays empty")
+    p.add_argument("--reassign_labels", metavar="PATH.npy", help="with --reassign: also write the final labels in the format "
+                   "--labels reads")
     args = p.parse_args(argv)
     args.train_argv = train_argv
+    if args.reassign and args.refine is None:
+        p.error("--reassign needs --refine")
+    if args.reassign_labels is not None:
+        if not args.reassign:
+            p.error("--reassign_labels needs --reassign")
+        if os.path.splitext(args.reassign_labels)[1] != ".npy":
+            p.error("--reassign_labels must end in .npy (got %s)" % args.reassign_labels)
     if args.refine is None:
         for name in ("refine_angles", "refine_step", "refine_shift"):
             if vars(args)[name] is not None:
@@ -224,6 +239,10 @@ def infer_arguments(argv=None):
         if args.frc and args.label_array.size and args.label_array.max() + 1 > INFER_FRC_MAX_CLASSES:
             p.error("--frc keeps two sums per class: at most %d classes (--labels has %d)"
                     % (INFER_FRC_MAX_CLASSES, args.label_array.max() + 1))
+    classes = args.cluster if args.cluster is not None else 1 if args.label_array is None or not args.label_array.size \
+        else int(args.label_array.max()) + 1
+    if args.reassign and classes > INFER_MAX_REASSIGN_CLASSES:
+        p.error("--reassign scores every image against every class: at most %d classes (got %d)" % (INFER_MAX_REASSIGN_CLASSES, classes))
     return args
 
 
@@ -476,9 +495,10 @@ class Accumulators(object):
     def _align(self, y, per_image, q_mu):
         return E.align_minibatch(y, self.n, self.m, per_image, q_mu, self.rotate, self.translate, self.pose, self.interp)
 
-    def _half_labels(self, lo, hi):
-        """label_d[lo:hi] with class k split by the parity of the dataset index: 2k + (i & 1); -1 stays -1."""
-        label = self.label_d[lo:hi]
+    def _half_labels(self, lo, hi, label=None):
+        """label_d[lo:hi] (or `label`, the labels of those images) with class k split by the parity of the dataset index:
+        2k + (i & 1); -1 stays -1."""
+        label = self.label_d[lo:hi] if label is None else label
         parity = torch.arange(lo, hi, dtype=torch.int32, device=label.device) & 1
         return torch.where(label >= 0, 2 * label + parity, label).contiguous()
 
@@ -508,14 +528,15 @@ class Accumulators(object):
             return y
         return ops.ctf_apply(y, self.table_d[lo:lo + y.size(0)], self.n, self.m, self.ctf_scale, "flip")
 
-    def update_at(self, lo, seen, pose3):
+    def update_at(self, lo, seen, pose3, label=None):
         """refine_walk's half of align_and_update: `seen` aligned at the poses pose3 (B, 3) and added to the class sums (and the
-        half-set sums) under label_d.  --refine excludes the Wiener sums."""
+        half-set sums) under label_d, or under `label` (B) int32 where --reassign has moved the images.  --refine excludes the
+        Wiener sums."""
         hi = lo + seen.size(0)
         aligned, cover = E.align_at(seen, self.n, self.m, pose3, self.rotate, self.translate, self.interp)
-        self.sums.update(aligned, cover, self.label_d[lo:hi])
+        self.sums.update(aligned, cover, self.label_d[lo:hi] if label is None else label)
         if self.halves is not None:
-            self.halves.update(aligned, cover, self._half_labels(lo, hi))
+            self.halves.update(aligned, cover, self._half_labels(lo, hi, label))
         return aligned
 
     def keep(self, name, lo, images):
@@ -586,7 +607,12 @@ def refine_walk(args, facts, split, acc, rows, lay):
     the image align_and_update would align is searched around its stored pose (elbo.refine_poses under elbo.refine_mask), the
     new pose stored, the image aligned at it and the update calls made.  The last round fills --aligned again.  A coordinate
     the model does not infer is not searched.  Nothing is read back between or inside rounds; acc.refined keeps what the files
-    report, the accumulators and (under --frc) the curves from before the first round among it."""
+    report, the accumulators and (under --frc) the curves from before the first round among it.
+
+    --reassign: the round scores each labelled image against all K references (under --frc the K of its own half: slot k holds
+    2k + (i & 1)) with elbo.classify_poses, takes the winning slot as its label for this round's updates and the next round's
+    search, and the pose refined against that winner.  An image with no live slot keeps label and pose.  The round's labels go
+    into a new tensor, swapped in at its end as the poses are."""
     n, m, bs, device = facts.n, facts.m, args.minibatch_size, acc.device
     A = args.refine_angles if facts.rotate else 0
     S = args.refine_shift if facts.translate else 0
@@ -601,6 +627,14 @@ def refine_walk(args, facts, split, acc, rows, lay):
     source = acc.halves if args.frc else acc.sums
     score = torch.zeros(facts.images, args.refine, dtype=torch.float64, device=device)
     offset = torch.zeros(facts.images, args.refine, 4, dtype=torch.int32, device=device)
+    moves = None
+    if args.reassign:
+        K, label = acc.sums.n_classes, acc.label_d
+        slots = torch.arange(K, dtype=torch.int32, device=device).unsqueeze(0)
+        moves = {"labels": torch.zeros(facts.images, args.refine, dtype=torch.int32, device=device),
+                 "moved": torch.zeros(args.refine, dtype=torch.int64, device=device),
+                 "class_score": torch.zeros(facts.images, K, dtype=torch.float64, device=device),
+                 "margin": torch.zeros(facts.images, args.refine, dtype=torch.float64, device=device)}
     for r in range(args.refine):
         ref = class_means(source)                   # a new tensor: the accumulators can be zeroed
         for t in (acc.sums, acc.halves):
@@ -608,19 +642,39 @@ def refine_walk(args, facts, split, acc, rows, lay):
                 t.sum.zero_()
                 t.count.zero_()
         new_pose = torch.empty_like(pose)
+        new_label = torch.empty_like(label) if args.reassign else None
         for lo in range(0, facts.images, bs):
             hi = min(lo + bs, facts.images)
             seen = acc.seen(lo, split.data[lo:hi])
-            ref_index = acc._half_labels(lo, hi) if args.frc else acc.label_d[lo:hi].contiguous()
-            found = E.refine_poses(seen, n, m, ref, weight, ref_index, pose[lo:hi].contiguous(), A, step, S, acc.interp)
+            moved_to = None
+            if args.reassign:
+                old = label[lo:hi]
+                parity = torch.arange(lo, hi, dtype=torch.int32, device=device).unsqueeze(1) & 1
+                cand = torch.where(old.unsqueeze(1) >= 0, 2 * slots + parity if args.frc else slots.expand(hi - lo, K), -1)
+                picked, found = E.classify_poses(seen, n, m, ref, weight, cand.to(torch.int32).contiguous(), pose[lo:hi].contiguous(),
+                                                 A, step, S, acc.interp)
+                moved_to = torch.where(picked.choice >= 0, picked.choice, old).contiguous()
+                new_label[lo:hi] = moved_to
+                moves["margin"][lo:hi, r] = picked.margin
+                if r == args.refine - 1:
+                    moves["class_score"][lo:hi] = picked.cand_score
+            else:
+                ref_index = acc._half_labels(lo, hi) if args.frc else acc.label_d[lo:hi].contiguous()
+                found = E.refine_poses(seen, n, m, ref, weight, ref_index, pose[lo:hi].contiguous(), A, step, S, acc.interp)
             new_pose[lo:hi] = found.pose
             score[lo:hi, r] = found.score
             offset[lo:hi, r] = found.offset
-            aligned = acc.update_at(lo, seen, found.pose)
+            aligned = acc.update_at(lo, seen, found.pose, moved_to)
             if r == args.refine - 1 and "aligned" in acc.stacks:
                 acc.keep("aligned", lo, aligned)
         pose = new_pose
+        if args.reassign:
+            moves["labels"][:, r] = new_label
+            moves["moved"][r] = (new_label != label).sum()
+            label = new_label
     acc.refined = dict(before, pose=pose, score=score, offset=offset)
+    if args.reassign:
+        acc.refined.update(moves, label=label)
 
 
 def frc_finish(args, facts, acc):
@@ -671,6 +725,12 @@ def collect(args, facts, lay, rows, acc, fit, centres):
         meta.update(refine=args.refine, refine_angles=args.refine_angles, refine_step=args.refine_step, refine_shift=args.refine_shift)
         arrays.update(pose_refined=acc.refined["pose"].cpu().numpy(), refine_score=acc.refined["score"].cpu().numpy(),
                       refine_offset=acc.refined["offset"].cpu().numpy())
+        if args.reassign:
+            meta.update(reassign=True, reassign_labels=args.reassign_labels)
+            arrays.update(label_refined=acc.refined["label"].cpu().numpy().astype(np.int64),
+                          refine_label=acc.refined["labels"].cpu().numpy(), refine_moved=acc.refined["moved"].cpu().numpy(),
+                          refine_class_score=acc.refined["class_score"].cpu().numpy(),
+                          refine_class_margin=acc.refined["margin"].cpu().numpy())
     found, labels = None, acc.labels
     if fit is not None:
         meta.update(pose=args.pose, cluster=args.cluster, cluster_out=args.cluster_out, cluster_labels=args.cluster_labels,
@@ -700,12 +760,16 @@ def _host_average(total, count, shape):
 def class_arrays(args, facts, acc, labels):
     """The arrays of --class_averages: sums, counts, averages and members per class; under --ctf_correct wiener also the Wiener
     averages with their numerator and denominator (another lambda needs no second run); under --refine those of the last round,
-    and average_unrefined from before the first."""
+    and average_unrefined from before the first; under --reassign members (and half_members) are those of the final labels, and
+    members_unrefined those of `labels`."""
     n, m, sums = facts.n, facts.m, acc.sums
     shape = (sums.n_classes, n, m, facts.channels)
     total, count, average = _host_average(*sums.result(), shape)
     members = np.bincount(labels[labels >= 0], minlength=sums.n_classes).astype(np.int64)
     classes = {"sum": total, "count": count, "average": average, "members": members}
+    if args.reassign:
+        labels = acc.refined["label"].cpu().numpy().astype(np.int64)
+        classes.update(members=np.bincount(labels[labels >= 0], minlength=sums.n_classes).astype(np.int64), members_unrefined=members)
     if acc.refined is not None:
         classes["average_unrefined"] = _host_average(acc.refined["sum"], acc.refined["count"], shape)[2]
     if acc.wiener is not None:
@@ -756,6 +820,8 @@ def write_outputs(args, facts, acc, arrays, found, labels):
         write_npz(args.cluster_out, found)
         if args.cluster_labels is not None:
             write_atomically(args.cluster_labels, lambda f: np.save(f, labels))
+    if args.reassign_labels is not None:
+        write_atomically(args.reassign_labels, lambda f: np.save(f, arrays["label_refined"]))
     write_npz(args.out, arrays)
 
 

@@ -52,7 +52,8 @@ def _p(t):
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
                  for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES,
                                              **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES,
-                                             **_lib.FRC_SIGNATURES, **_lib.REFINE_SIGNATURES}.items()}
+                                             **_lib.FRC_SIGNATURES, **_lib.REFINE_SIGNATURES,
+                                             **_lib.CLASSIFY_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -860,6 +861,51 @@ def pose_search(y, ref, weight, ref_index, pose, rows, cols, angles, step, shift
     _call("svae_pose_search", dev, yc, ref.contiguous(), weight, ref_index.contiguous(), pose.contiguous(), B, n_ref, rows, cols, C,
           A, float(step), S, _lib.ALIGN_INTERP[interp], out, score, offset, scores, ws, ws_bytes)
     return PoseSearch(out, score, offset, scores)
+
+
+PoseClassify = namedtuple("PoseClassify", "choice ref_chosen cand_score margin")
+
+
+def pose_classify(y, ref, weight, cand, pose, rows, cols, angles, step, shift, interp="bicubic", return_margin=True):
+    """Each image scored against several references over pose_search's neighbourhood (svae_pose_classify,
+    include/svae_classify.h): cand (B, M) int32 names the references of image b slot by slot, an entry outside [0, n_ref) being
+    an empty slot; every other argument is pose_search's.  cand_score[b, j] is the best score of the search against ref[cand[b, j]],
+    bit for bit what pose_search returns for it, or -inf where that search skips; choice is the first slot of the highest score
+    (-1: none), ref_chosen its reference, margin the winner's lead over the best other live slot (+inf with fewer than two).
+    Returns PoseClassify(choice (B) int32, ref_chosen (B) int32, cand_score (B, M) float64, margin (B) float64 or None) on the
+    device; the pose is not refined (pose_search with ref_index = ref_chosen does that) and nothing is read back."""
+    for name, t in (("y", y), ("ref", ref), ("cand", cand), ("pose", pose)):
+        _require_hip(t, name)
+    if interp not in _lib.ALIGN_INTERP:
+        raise RuntimeError("pose_classify: interp must be one of %s, got %r" % (sorted(_lib.ALIGN_INTERP), interp))
+    B, N = y.size(0), rows * cols
+    yc = _f32(y)
+    C = yc.numel() // (B * N) if B * N else 0
+    if C < 1 or C * B * N != yc.numel():
+        raise RuntimeError("pose_classify: y %s does not hold %d images of %dx%d" % (tuple(y.shape), B, rows, cols))
+    if ref.dtype != torch.float64 or ref.numel() % (N * C) or not ref.numel():
+        raise RuntimeError("pose_classify: ref %s (%s) must be float64 planes of %dx%dx%d" % (tuple(ref.shape), ref.dtype, rows, cols, C))
+    n_ref = ref.numel() // (N * C)
+    if weight is not None:
+        _require_hip(weight, "weight")
+        if weight.dtype != torch.float64 or weight.numel() != N:
+            raise RuntimeError("pose_classify: weight must be %d float64 values, got %s (%s)" % (N, tuple(weight.shape), weight.dtype))
+        weight = weight.contiguous()
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.size(0) != B or cand.size(1) < 1:
+        raise RuntimeError("pose_classify: cand must be (%d, M >= 1) int32, got %s (%s)" % (B, tuple(cand.shape), cand.dtype))
+    if pose.dtype != torch.float32 or tuple(pose.shape) != (B, 3):
+        raise RuntimeError("pose_classify: pose must be (%d, 3) float32, got %s (%s)" % (B, tuple(pose.shape), pose.dtype))
+    A, S, M = int(angles), int(shift), cand.size(1)
+    dev = y.device
+    choice = torch.empty(B, dtype=torch.int32, device=dev)
+    ref_chosen = torch.empty(B, dtype=torch.int32, device=dev)
+    cand_score = torch.empty(B, M, dtype=torch.float64, device=dev)
+    margin = torch.empty(B, dtype=torch.float64, device=dev) if return_margin else None
+    ws_bytes = _lib.lib().svae_pose_classify_workspace_bytes(B, n_ref, M, rows, cols, C)   # the norms, + plane slices above the LDS limit
+    ws = _buf(dev, ws_bytes, "classify")
+    _call("svae_pose_classify", dev, yc, ref.contiguous(), weight, cand.contiguous(), pose.contiguous(), B, n_ref, M, rows, cols, C,
+          A, float(step), S, _lib.ALIGN_INTERP[interp], choice, ref_chosen, cand_score, margin, ws, ws_bytes)
+    return PoseClassify(choice, ref_chosen, cand_score, margin)
 
 
 KMeansFit = namedtuple("KMeansFit", "label centres members record seed_index")
