@@ -192,6 +192,21 @@ CLASSIFY_SIGNATURES = {
 }
 
 
+# ---- include/svae_gmm.h: the diagonal-covariance Gaussian mixture, a ninth header with a table of its own ----
+# Same rules (tests/test_gmm_cpu.py holds these rows, and the mirror of the header's one struct, to that header).  `rec` is the
+# address of a record in device memory.  The header adds no constant.
+class GmmRecord(ctypes.Structure):
+    """svae_gmm_record: all zero bytes = a fresh record."""
+    _fields_ = [("iterations", i64), ("converged_at", i64), ("assigned", i64), ("dead", i64), ("loglik", f64), ("previous", f64)]
+
+
+GMM_SIGNATURES = {
+    "svae_gmm_workspace_bytes": (sz, [i64, i32, i32]),
+    "svae_gmm_init": (cint, [vp, i64, i32, i32, vp, f64, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "svae_gmm_step": (cint, [vp, i64, i32, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -216,7 +231,7 @@ def lib():
     L = ctypes.CDLL(path)
     for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES,
                                       **CLUSTER_SIGNATURES, **FRC_SIGNATURES, **REFINE_SIGNATURES,
-                                      **CLASSIFY_SIGNATURES}.items():
+                                      **CLASSIFY_SIGNATURES, **GMM_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

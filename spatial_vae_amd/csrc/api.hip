@@ -20,6 +20,7 @@
 #include "../../include/svae_frc.h"
 #include "../../include/svae_refine.h"
 #include "../../include/svae_classify.h"
+#include "../../include/svae_gmm.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
@@ -31,6 +32,7 @@
 #include "refine.h"
 #include "classify.h"
 #include "cluster.h"
+#include "gmm.h"
 #include "encoder.h"
 #include "split.h"
 
@@ -2103,6 +2105,80 @@ int svae_kmeans_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t up
     hipLaunchKernelGGL(kmeans_tail_kernel, dim3(blocks_for(up ? (long)k * D : (long)k)), dim3(256), 0, st, D, k, chunks, up, centres, mem,
                        rec, w);
     return launch_status("svae_kmeans_step");
+}
+
+// ---- the Gaussian mixture over the content latents (include/svae_gmm.h) ----
+namespace {
+// the pointer, range, geometry and workspace rules the two mixture calls share; 0 or the refusal
+int gmm_check(const char* who, const void* x, int64_t N, int32_t D, int32_t k, const void* labels, double reg, double tol,
+              const void* weight, const void* mean, const void* var, const void* resp, const void* loglik_point, const void* rec,
+              const void* ws, size_t ws_bytes) {
+    if (!x || !labels || !weight || !mean || !var || !resp || !rec)
+        return fail(SVAE_E_INVALID, "%s: null x, labels, weight, mean, var, resp or rec", who);
+    if (misaligned8(weight) || misaligned8(mean) || misaligned8(var) || misaligned8(resp) || misaligned8(rec) || misaligned8(loglik_point))
+        return fail(SVAE_E_INVALID, "%s: weight, mean, var, resp, loglik_point and rec must be 8-byte aligned", who);
+    if (!(reg > 0.0) || !std::isfinite(reg)) return fail(SVAE_E_INVALID, "%s: reg = %g must be a finite number > 0", who, reg);
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SVAE_E_INVALID, "%s: tol = %g must be a finite number >= 0", who, tol);
+    if (D < 1 || D > kKmeansMaxD || k < 1 || k > kKmeansMaxK || N < k || N > 0x7fffffffLL)
+        return fail(SVAE_E_INVALID, "%s: bad sizes N=%lld D=%d k=%d (1 <= D <= %d, 1 <= k <= %d, k <= N < 2^31)", who, (long long)N, D, k,
+                    kKmeansMaxD, kKmeansMaxK);
+    if (!ws) return fail(SVAE_E_WORKSPACE, "%s: null workspace", who);
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(SVAE_E_WORKSPACE, "%s: workspace not 256-byte aligned", who);
+    const size_t need = gmm_ws_words((long)N, D, k) * 8;
+    if (ws_bytes < need) return fail(SVAE_E_WORKSPACE, "%s: workspace too small: %zu < %zu", who, ws_bytes, need);
+    return SVAE_OK;
+}
+}  // namespace
+
+size_t svae_gmm_workspace_bytes(int64_t N, int32_t D, int32_t k) {
+    if (D < 1 || D > kKmeansMaxD || k < 1 || k > kKmeansMaxK || N < k || N > 0x7fffffffLL) return 0;
+    return gmm_ws_words((long)N, D, k) * 8;
+}
+
+int svae_gmm_init(const float* x, int64_t N, int32_t D, int32_t k, const int32_t* label_in, double reg, double* weight, double* mean,
+                  double* var, double* resp, svae_gmm_record* rec, void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (const int rc = gmm_check("svae_gmm_init", x, N, D, k, label_in, reg, 0.0, weight, mean, var, resp, nullptr, rec, ws, ws_bytes)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long P = kmeans_chunk((long)N);
+    const int chunks = (int)(((long)N + P - 1) / P);
+    const GmmWs w = gmm_ws(ws, (long)N, D, k);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(gmm_onehot_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, reinterpret_cast<const int*>(label_in), resp, w);
+    hipLaunchKernelGGL(gmm_accumulate_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean),
+                       static_cast<const double*>(resp), static_cast<const long long*>(nullptr), w);
+    hipLaunchKernelGGL(gmm_tail_kernel, dim3(blocks_for((long)k * (D + 1))), dim3(256), 0, st, D, k, chunks, (int)kGmmInit, reg, 0.0, weight,
+                       mean, var, rec, w);
+    return launch_status("svae_gmm_init");
+}
+
+int svae_gmm_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t update, double reg, double tol, double* weight,
+                  double* mean, double* var, double* resp, int32_t* label, double* loglik_point, svae_gmm_record* rec, void* ws,
+                  size_t ws_bytes, svae_stream_t stream) {
+    if (const int rc = gmm_check("svae_gmm_step", x, N, D, k, label, reg, tol, weight, mean, var, resp, loglik_point, rec, ws, ws_bytes))
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long P = kmeans_chunk((long)N);
+    const int chunks = (int)(((long)N + P - 1) / P);
+    const GmmWs w = gmm_ws(ws, (long)N, D, k);
+    int* lab = reinterpret_cast<int*>(label);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(gmm_prologue_kernel, dim3(blocks_for((long)k)), dim3(256), 0, st, D, k, static_cast<const double*>(weight),
+                       static_cast<const double*>(var), static_cast<const svae_gmm_record*>(rec), w);
+    if (D <= 4)
+        hipLaunchKernelGGL(gmm_e_kernel<4>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean), resp, lab,
+                           loglik_point, w);
+    else if (D <= 16)
+        hipLaunchKernelGGL(gmm_e_kernel<16>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean), resp, lab,
+                           loglik_point, w);
+    else
+        hipLaunchKernelGGL(gmm_e_kernel<64>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean), resp, lab,
+                           loglik_point, w);
+    if (update)
+        hipLaunchKernelGGL(gmm_accumulate_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean),
+                           static_cast<const double*>(resp), static_cast<const long long*>(w.snap), w);
+    hipLaunchKernelGGL(gmm_tail_kernel, dim3(update ? blocks_for((long)k * (D + 1)) : 1), dim3(256), 0, st, D, k, chunks,
+                       update ? (int)kGmmStep : (int)kGmmLabelOnly, reg, tol, weight, mean, var, rec, w);
+    return launch_status("svae_gmm_step");
 }
 
 int svae_gemm_mode_set(int mode) {

@@ -349,6 +349,20 @@ def cluster_latents(points, k, iters, restarts=1, generator=None):
     return out
 
 
+def mixture_latents(points, kmeans_fit, iters, reg=1e-6, tol=1e-8, min_resp=0.0):
+    """A diagonal-covariance Gaussian mixture of the content latents `points` (N, D) on the device (ops.GaussianMixture), started
+    from `kmeans_fit`, the dict of cluster_latents: one component per k-means class.  Returns the GmmFit's device tensors by name
+    with "max_resp" (N) float64, the largest responsibility of each point, and "label_used" (N) int32 = the mixture's label
+    where max_resp >= min_resp and -1 elsewhere (and wherever the label already is -1).  Nothing is read back."""
+    points = points.float().contiguous()
+    k = kmeans_fit["centres"].size(0)
+    fit = ops.GaussianMixture(k, points.size(1), points.device).fit(points, kmeans_fit["label"], kmeans_fit["centres"], iters, reg, tol)
+    out = dict(fit._asdict())
+    out["max_resp"] = fit.resp.max(1).values
+    out["label_used"] = torch.where(out["max_resp"] >= float(min_resp), fit.label, torch.full_like(fit.label, -1)).contiguous()
+    return out
+
+
 def ring_layout(n, m):
     """The rings of an n x m plane (include/svae_frc.h): (L, R, ring_frequency) with L = min(n, m), R = L // 2 + 1 rings and
     ring r standing for ring_frequency[r] = r / L cycles per pixel."""

@@ -28,6 +28,8 @@ INFER_MAX_CLASSES = 4096    # classes of --labels (svae_class_sums_update's limi
 INFER_STACK_FORMATS = (".npy", ".mrcs")
 INFER_MAX_CLUSTERS = min(INFER_MAX_CLASSES, 1024)   # classes of --cluster (include/svae_cluster.h's limit on k)
 INFER_MAX_RESTARTS = 16
+INFER_MAX_GMM_ITERS = 1000
+INFER_MAX_GMM_RESP = 2 ** 28        # images * K of --cluster_gmm: the (images, K) float64 responsibilities stay within 2 GiB
 INFER_FRC_MAX_CLASSES = INFER_MAX_CLASSES // 2      # --frc keeps two half-set sums per class
 INFER_FRC_MAX_BOX = 1024    # include/svae_frc.h's limit on n and m
 FRC_THRESHOLDS = (("resolution_0143", 0.143), ("resolution_05", 0.5))
@@ -97,6 +99,16 @@ def infer_arguments(argv=None):
                    "of lowest inertia is kept, the first of equals" % INFER_MAX_RESTARTS)
     p.add_argument("--cluster_seed", type=int, default=None, metavar="S", help="seed of the generator the k-means++ uniforms come "
                    "from (default --seed)")
+    p.add_argument("--cluster_gmm", type=int, default=None, metavar="I", help="with --cluster: fit a diagonal-covariance Gaussian "
+                   "mixture to the content latents by I EM iterations (1..%d) on the device, started from the k-means result.  Its "
+                   "labels take the place of the k-means labels for everything downstream; --cluster_out keeps the k-means arrays "
+                   "and gains the mixture's (gmm_*): responsibilities, log-likelihood, BIC and AIC among them" % INFER_MAX_GMM_ITERS)
+    p.add_argument("--cluster_gmm_reg", type=float, default=None, metavar="X", help="with --cluster_gmm: added to every variance, "
+                   "X > 0 (default 1e-6: a convention, not a tuned value)")
+    p.add_argument("--cluster_gmm_tol", type=float, default=None, metavar="X", help="with --cluster_gmm: the fit is frozen once an "
+                   "iteration gains no more than X |log-likelihood|, X >= 0 (default 1e-8, a convention too)")
+    p.add_argument("--cluster_min_resp", type=float, default=None, metavar="P", help="with --cluster_gmm: an image whose largest "
+                   "responsibility is below P, 0 <= P < 1, is in no class (label -1; default 0, a convention too: every image stays)")
     p.add_argument("--frc", action="store_true", help="with --class_averages: also accumulate each class over two disjoint halves "
                    "(image i of the split in half i & 1) and add their sums, the Fourier ring correlation of the two half averages, "
                    "the resolution at the 0.143 and 0.5 thresholds and the full average filtered by sqrt(2 FRC / (1 + FRC)).  One "
@@ -186,6 +198,24 @@ def infer_arguments(argv=None):
             p.error("--cluster_iters must be >= 1")
         if not 1 <= args.cluster_restarts <= INFER_MAX_RESTARTS:
             p.error("--cluster_restarts must be in [1, %d]" % INFER_MAX_RESTARTS)
+    if args.cluster_gmm is None:
+        for name in ("cluster_gmm_reg", "cluster_gmm_tol", "cluster_min_resp"):
+            if vars(args)[name] is not None:
+                p.error("--%s needs --cluster_gmm" % name)
+    else:
+        if args.cluster is None:
+            p.error("--cluster_gmm needs --cluster")
+        if not 1 <= args.cluster_gmm <= INFER_MAX_GMM_ITERS:
+            p.error("--cluster_gmm must be in [1, %d] (got %d)" % (INFER_MAX_GMM_ITERS, args.cluster_gmm))
+        args.cluster_gmm_reg = 1e-6 if args.cluster_gmm_reg is None else args.cluster_gmm_reg
+        args.cluster_gmm_tol = 1e-8 if args.cluster_gmm_tol is None else args.cluster_gmm_tol
+        args.cluster_min_resp = 0.0 if args.cluster_min_resp is None else args.cluster_min_resp
+        if not 0 < args.cluster_gmm_reg < float("inf"):
+            p.error("--cluster_gmm_reg must be a finite number > 0 (got %r)" % args.cluster_gmm_reg)
+        if not 0 <= args.cluster_gmm_tol < float("inf"):
+            p.error("--cluster_gmm_tol must be a finite number >= 0 (got %r)" % args.cluster_gmm_tol)
+        if not 0 <= args.cluster_min_resp < 1:
+            p.error("--cluster_min_resp must be in [0, 1) (got %r)" % args.cluster_min_resp)
     if args.ctf_correct is not None and args.script != "particles":
         p.error("--ctf_correct is for particles (the script whose images have a CTF), not %s" % args.script)
     if args.ctf_correct == "flip" and args.aligned is None and args.class_averages is None:
@@ -420,6 +450,9 @@ def check_request(args, facts):
             _refuse("--cluster: this state is from before the run's z_delay ended (z_scale = 0): every content latent is 0")
         if args.cluster > images:
             _refuse("--cluster {} exceeds the {} images of the {} split".format(args.cluster, images, facts.split))
+        if args.cluster_gmm is not None and images * args.cluster > INFER_MAX_GMM_RESP:
+            _refuse("--cluster_gmm keeps a responsibility per image and class: {} images x {} classes exceed 2^28".format(
+                images, args.cluster))
     if args.refine is not None:
         if not facts.rotate and not facts.translate:
             _refuse("--refine searches rotations and shifts, and this model infers neither")
@@ -576,20 +609,28 @@ def score_walk(args, model, split, acc):
 def cluster_walk(args, model, split, acc, rows, lay):
     """--cluster: k-means of every image's content latents (the k-means++ uniforms from a fresh host generator seeded with
     --cluster_seed), then for --class_averages a second walk over the minibatches that re-aligns from the stored rows and makes
-    the update calls the scoring walk would have made, in its order; no host read in between.  Returns (the fit of
-    elbo.cluster_latents, the decoder's un-posed reconstruction of the centres)."""
+    the update calls the scoring walk would have made, in its order; no host read in between.  Under --cluster_gmm the mixture
+    of elbo.mixture_latents is fitted on the chosen restart's k-means fit and ITS labels (-1 below --cluster_min_resp) are what
+    every later stage sees.  Returns (the fit of elbo.cluster_latents, with the mixture's tensors under "gmm" and the decoder's
+    un-posed reconstruction of its means under "gmm_mean_recon"; the decoder's un-posed reconstruction of the centres)."""
     per_image, q_mu, _ = split_rows(torch.cat(rows), lay)
     zc = E.content_latents(per_image, q_mu, model.cfg["rotate"], model.cfg["translate"], args.pose)
     kgen = torch.Generator()
     kgen.manual_seed(args.cluster_seed)
     fit = E.cluster_latents(zc, args.cluster, args.cluster_iters, args.cluster_restarts, kgen)
     acc.label_d = fit["label"]
+    if args.cluster_gmm is not None:
+        fit["gmm"] = E.mixture_latents(zc, fit, args.cluster_gmm, args.cluster_gmm_reg, args.cluster_gmm_tol, args.cluster_min_resp)
+        acc.label_d = fit["gmm"]["label_used"]
     if acc.sums is not None:
         for i, lo in enumerate(range(0, split.data.size(0), args.minibatch_size)):
             per_image, q_mu, _ = split_rows(rows[i], lay)
             acc.align_and_update(lo, split.data[lo:lo + args.minibatch_size], per_image, q_mu, True)
     centres = E.reconstruct_unposed(split.x, model.p_net, args.cluster, fit["centres"].float(),
                                     gaussian_mean=(args.script == "particles"))
+    if args.cluster_gmm is not None:
+        fit["gmm_mean_recon"] = E.reconstruct_unposed(split.x, model.p_net, args.cluster, fit["gmm"]["mean"].float(),
+                                                      gaussian_mean=(args.script == "particles"))
     return fit, centres
 
 
@@ -741,12 +782,37 @@ def collect(args, facts, lay, rows, acc, fit, centres):
                  "inertia": np.float64(record["inertia"]), "iterations": np.int64(record["iterations"]),
                  "converged_at": np.int64(record["converged_at"]), "seed_index": fit["seed_index"].cpu().numpy().astype(np.int64),
                  "restart_inertia": fit["restart_inertia"].cpu().numpy(), "chosen_restart": np.int64(fit["chosen_restart"].item()),
-                 "centre_recon": centres.cpu().numpy().reshape(args.cluster, facts.n, facts.m, -1),
-                 "meta": np.array(json.dumps(meta))}
+                 "centre_recon": centres.cpu().numpy().reshape(args.cluster, facts.n, facts.m, -1)}
+        if args.cluster_gmm is not None:
+            meta.update(cluster_gmm=args.cluster_gmm, cluster_gmm_reg=args.cluster_gmm_reg, cluster_gmm_tol=args.cluster_gmm_tol,
+                        cluster_min_resp=args.cluster_min_resp)
+            found.update(mixture_arrays(args, facts, fit))
+            labels = found["gmm_label_used"]
+        found["meta"] = np.array(json.dumps(meta))
     arrays["meta"] = np.array(json.dumps(meta))
     summary = "images {}\tbound {!r}\tlog p(x|z) {!r}\tKL {!r}\tmedian ESS {:.3f}".format(
         host.shape[0], means[0], means[1], means[2], float(np.median(arrays["ess"])))
     return arrays, found, labels, summary
+
+
+def mixture_arrays(args, facts, fit):
+    """The arrays --cluster_gmm adds to --cluster_out, transferred once; BIC and AIC are formed here on the host from the final
+    log-likelihood L: p = (live - 1) + 2 live D free parameters, BIC = -2 L + p ln(assigned), AIC = -2 L + 2 p."""
+    gmm = {k: v.cpu().numpy() for k, v in fit["gmm"].items()}
+    record = ops.GaussianMixture.read_record(fit["gmm"]["record"])
+    K, D = gmm["mean"].shape
+    used = gmm["label_used"].astype(np.int64)
+    live = K - record["dead"]
+    p = (live - 1) + 2 * live * D
+    L = record["loglik"]
+    return {"gmm_weight": gmm["weight"], "gmm_mean": gmm["mean"], "gmm_var": gmm["var"], "gmm_resp": gmm["resp"],
+            "gmm_max_resp": gmm["max_resp"], "gmm_label": gmm["label"].astype(np.int64), "gmm_label_used": used,
+            "gmm_members": np.bincount(used[used >= 0], minlength=K).astype(np.int64), "gmm_loglik_point": gmm["loglik_point"],
+            "gmm_loglik": np.float64(L), "gmm_loglik_trace": gmm["trace"], "gmm_iterations": np.int64(record["iterations"]),
+            "gmm_converged_at": np.int64(record["converged_at"]), "gmm_dead": np.int64(record["dead"]),
+            "gmm_bic": np.float64(-2.0 * L + p * math.log(record["assigned"]) if record["assigned"] > 0 else np.nan),
+            "gmm_aic": np.float64(-2.0 * L + 2.0 * p),
+            "gmm_mean_recon": fit["gmm_mean_recon"].cpu().numpy().reshape(K, facts.n, facts.m, -1)}
 
 
 def _host_average(total, count, shape):

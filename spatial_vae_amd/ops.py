@@ -53,7 +53,7 @@ _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib
                  for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES,
                                              **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES,
                                              **_lib.FRC_SIGNATURES, **_lib.REFINE_SIGNATURES,
-                                             **_lib.CLASSIFY_SIGNATURES}.items()}
+                                             **_lib.CLASSIFY_SIGNATURES, **_lib.GMM_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -968,6 +968,77 @@ class KMeans:
         ctypes.memmove(ctypes.byref(rec), record.cpu().numpy().tobytes(), ctypes.sizeof(rec))
         out = {name: int(getattr(rec, name)) for name, _ in _lib.KMeansRecord._fields_[:-1]}
         out["inertia"] = float(rec.inertia)
+        return out
+
+
+GmmFit = namedtuple("GmmFit", "weight mean var resp label loglik_point record trace")
+
+
+class GaussianMixture:
+    """A diagonal-covariance Gaussian mixture of (N, D) fp32 points with k components, fitted by EM on the device from a k-means
+    result (include/svae_gmm.h).  Every sum has a fixed order and nothing is atomic, so the same inputs give the same bits;
+    nothing is read back.  A point with a non-finite coordinate gets the label -1 and an all-zero row of responsibilities."""
+
+    RECORD_WORDS = ctypes.sizeof(_lib.GmmRecord) // 8
+
+    def __init__(self, k, D, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("spatial_vae_amd: GaussianMixture must live on a HIP device (got %s); the MI355X path has no CPU "
+                               "fallback" % device)
+        self.k, self.D, self.device = int(k), int(D), device
+        if not (1 <= self.k <= 1024 and 1 <= self.D <= 64):
+            raise RuntimeError("GaussianMixture: k = %d must be in 1..1024 and D = %d in 1..64" % (self.k, self.D))
+
+    def fit(self, points, label, centres, iters, reg=1e-6, tol=1e-8):
+        """svae_gmm_init from the k-means `label` (N) int32 and `centres` (k, D) float64, `iters` update steps and one labelling
+        step, all enqueued on the current stream; after each step the record's loglik is copied device-to-device into trace.
+        points: (N, D) fp32 contiguous on the device, N >= k.  Returns GmmFit of device tensors: weight (k), mean (k, D),
+        var (k, D) and resp (N, k) float64, label (N) int32, loglik_point (N) float64, record (the svae_gmm_record as 6 int64
+        words, see read_record) and trace (iters + 1) float64.  The inputs are left as they were."""
+        _require_hip(points, "points")
+        if points.dtype != torch.float32 or points.dim() != 2 or points.size(1) != self.D or not points.is_contiguous():
+            raise RuntimeError("GaussianMixture.fit: points must be a contiguous (N, %d) float32 tensor, got %s %s"
+                               % (self.D, tuple(points.shape), points.dtype))
+        N, iters, reg, tol = points.size(0), int(iters), float(reg), float(tol)
+        dev, k, D = self.device, self.k, self.D
+        if N < k or iters < 0:
+            raise RuntimeError("GaussianMixture.fit: %d points for k = %d, iters = %d" % (N, k, iters))
+        if not (math.isfinite(reg) and reg > 0 and math.isfinite(tol) and tol >= 0):
+            raise RuntimeError("GaussianMixture.fit: reg = %r must be finite and > 0, tol = %r finite and >= 0" % (reg, tol))
+        if not torch.is_tensor(label) or label.dtype != torch.int32 or tuple(label.shape) != (N,) or not label.is_cuda:
+            raise RuntimeError("GaussianMixture.fit: label must be %d int32 numbers on the device" % N)
+        if not torch.is_tensor(centres) or centres.dtype != torch.float64 or tuple(centres.shape) != (k, D) or not centres.is_cuda:
+            raise RuntimeError("GaussianMixture.fit: centres must be a (%d, %d) float64 tensor on the device" % (k, D))
+        ws_bytes = _lib.lib().svae_gmm_workspace_bytes(N, D, k)
+        if ws_bytes == 0:
+            raise RuntimeError("GaussianMixture.fit: bad geometry N = %d, D = %d, k = %d" % (N, D, k))
+        ws = _buf(dev, ws_bytes, "gmm")
+        f64 = dict(dtype=torch.float64, device=dev)
+        out = GmmFit(torch.empty(k, **f64), centres.contiguous().clone(), torch.empty(k, D, **f64), torch.empty(N, k, **f64),
+                     torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, **f64),
+                     torch.zeros(self.RECORD_WORDS, dtype=torch.int64, device=dev), torch.empty(iters + 1, **f64))
+        _call("svae_gmm_init", dev, points, N, D, k, label.contiguous(), reg, out.weight, out.mean, out.var, out.resp, out.record, ws,
+              ws.numel())
+        loglik = self.loglik(out.record)
+        for i, update in enumerate([1] * iters + [0]):
+            _call("svae_gmm_step", dev, points, N, D, k, update, reg, tol, out.weight, out.mean, out.var, out.resp, out.label,
+                  out.loglik_point, out.record, ws, ws.numel())
+            out.trace[i:i + 1].copy_(loglik)
+        return out
+
+    @staticmethod
+    def loglik(record):
+        """The record's loglik as a one-element float64 device tensor (a view: no synchronisation)."""
+        return record[_lib.GmmRecord.loglik.offset // 8:][:1].view(torch.float64)
+
+    @staticmethod
+    def read_record(record):
+        """{iterations, converged_at, assigned, dead, loglik, previous} of a record tensor: synchronises."""
+        rec = _lib.GmmRecord()
+        ctypes.memmove(ctypes.byref(rec), record.cpu().numpy().tobytes(), ctypes.sizeof(rec))
+        out = {name: int(getattr(rec, name)) for name, _ in _lib.GmmRecord._fields_[:4]}
+        out.update(loglik=float(rec.loglik), previous=float(rec.previous))
         return out
 
 
