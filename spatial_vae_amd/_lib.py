@@ -207,6 +207,17 @@ GMM_SIGNATURES = {
 }
 
 
+# ---- include/svae_expect.h: maximum-likelihood class averages, a tenth header with a table of its own ----
+# Same rules (tests/test_expect_cpu.py holds these rows to that header's prototypes).  The header adds no constant: `interp`
+# takes the values of ALIGN_INTERP.
+EXPECT_SIGNATURES = {
+    "svae_pose_expect_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "svae_pose_expect": (cint, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f64, i32, i32, f64, vp, vp, vp, vp, vp,
+                                vp, sz, vp]),
+    "svae_expect_sums_update": (cint, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -231,7 +242,7 @@ def lib():
     L = ctypes.CDLL(path)
     for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES,
                                       **CLUSTER_SIGNATURES, **FRC_SIGNATURES, **REFINE_SIGNATURES,
-                                      **CLASSIFY_SIGNATURES, **GMM_SIGNATURES}.items():
+                                      **CLASSIFY_SIGNATURES, **GMM_SIGNATURES, **EXPECT_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

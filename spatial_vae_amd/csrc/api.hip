@@ -21,6 +21,7 @@
 #include "../../include/svae_refine.h"
 #include "../../include/svae_classify.h"
 #include "../../include/svae_gmm.h"
+#include "../../include/svae_expect.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
@@ -33,6 +34,7 @@
 #include "classify.h"
 #include "cluster.h"
 #include "gmm.h"
+#include "expect.h"
 #include "encoder.h"
 #include "split.h"
 
@@ -2179,6 +2181,87 @@ int svae_gmm_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t updat
     hipLaunchKernelGGL(gmm_tail_kernel, dim3(update ? blocks_for((long)k * (D + 1)) : 1), dim3(256), 0, st, D, k, chunks,
                        update ? (int)kGmmStep : (int)kGmmLabelOnly, reg, tol, weight, mean, var, rec, w);
     return launch_status("svae_gmm_step");
+}
+
+// ---- maximum-likelihood class averages (include/svae_expect.h) ----
+namespace {
+bool expect_sizes_ok(int B, int n_ref, int M, int rows, int cols, int C, int A, int S) {
+    return refine_sizes_ok(B, rows, cols, C, A, S) && n_ref >= 1 && M >= 1 && M <= kExpectMaxSlots &&
+           (long)B * rows * cols * C <= 0x7fffffffL && (long)n_ref * rows * cols * C <= 0x7fffffffL &&
+           (long)B * M * rows * cols * C <= 0x7fffffffL;
+}
+// doubles one workgroup keeps beside the fixed ones: the resampled plane, its coverage and the M log-weight volumes
+size_t expect_doubles(int M, int rows, int cols, int C, int A, int S) {
+    return (size_t)rows * cols * C + (size_t)rows * cols + (size_t)M * (2 * A + 1) * (2 * S + 1) * (2 * S + 1);
+}
+bool expect_in_lds(int M, int rows, int cols, int C, int A, int S) {
+    return (expect_doubles(M, rows, cols, C, A, S) + kExpectFixed) * sizeof(double) <= CTF_LDS_MAX;
+}
+}  // namespace
+
+size_t svae_pose_expect_workspace_bytes(int32_t B, int32_t n_ref, int32_t M, int32_t rows, int32_t cols, int32_t C, int32_t A,
+                                        int32_t S) {
+    if (!expect_sizes_ok(B, n_ref, M, rows, cols, C, A, S)) return 0;
+    size_t doubles = roundup32((size_t)n_ref);
+    if (!expect_in_lds(M, rows, cols, C, A, S)) doubles += (size_t)dft_groups(B) * roundup32(expect_doubles(M, rows, cols, C, A, S));
+    return doubles * sizeof(double);
+}
+
+int svae_pose_expect(const float* y, const double* ref, const double* weight, const double* log_prior, const int32_t* cand,
+                     const float* pose_in, int32_t B, int32_t n_ref, int32_t M, int32_t rows, int32_t cols, int32_t C, int32_t A,
+                     double step, int32_t S, int32_t interp, double inv_sigma2, double* contrib, double* cover_w,
+                     double* class_post, double* log_evidence, int32_t* best, void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (!refine_sizes_ok(B, rows, cols, C, A, S) || n_ref < 1 || M < 1 || M > kExpectMaxSlots)
+        return fail(SVAE_E_INVALID, "svae_pose_expect: bad sizes B=%d n_ref=%d M=%d rows=%d cols=%d C=%d A=%d S=%d (M in 1..%d, rows, "
+                    "cols in 2..1024, C in 1..%d, A in 0..32, S in 0..8)", B, n_ref, M, rows, cols, C, A, S, kExpectMaxSlots, SVAE_MAX_OUT);
+    if (!expect_sizes_ok(B, n_ref, M, rows, cols, C, A, S))
+        return fail(SVAE_E_INVALID, "svae_pose_expect: %d images or %d references of %d x %d x %d, or %d x %d contribution rows, are too "
+                    "many", B, n_ref, rows, cols, C, B, M);
+    if (A > 0 && (!(step > 0.0) || isinf(step))) return fail(SVAE_E_INVALID, "svae_pose_expect: step must be finite and > 0 where A > 0");
+    if (interp != SVAE_ALIGN_BILINEAR && interp != SVAE_ALIGN_BICUBIC)
+        return fail(SVAE_E_INVALID, "svae_pose_expect: unknown interpolation %d", interp);
+    if (!(inv_sigma2 >= 0.0) || !std::isfinite(inv_sigma2))
+        return fail(SVAE_E_INVALID, "svae_pose_expect: inv_sigma2 = %g must be a finite number >= 0", inv_sigma2);
+    if (!y || !ref || !cand || !pose_in || !contrib || !cover_w || !class_post || !log_evidence || !best)
+        return fail(SVAE_E_INVALID, "svae_pose_expect: null y, ref, cand, pose_in, contrib, cover_w, class_post, log_evidence or best");
+    const bool scratch = !expect_in_lds(M, rows, cols, C, A, S);
+    const size_t need = svae_pose_expect_workspace_bytes(B, n_ref, M, rows, cols, C, A, S);
+    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
+        return fail(SVAE_E_INVALID, "svae_pose_expect: %d references and %d x %d x %d images with M=%d, A=%d, S=%d need a workspace of "
+                    "%zu bytes, 256-byte aligned (got %zu)", n_ref, rows, cols, C, M, A, S, need, ws_bytes);
+    using K = decltype(&pose_expect_kernel<false, false>);
+    const bool cubic = interp == SVAE_ALIGN_BICUBIC;
+    K kernel = scratch ? (cubic ? pose_expect_kernel<true, true> : pose_expect_kernel<false, true>)
+                       : (cubic ? pose_expect_kernel<true, false> : pose_expect_kernel<false, false>);
+    const size_t lds = ((scratch ? 0 : expect_doubles(M, rows, cols, C, A, S)) + kExpectFixed) * sizeof(double);
+    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return fail(SVAE_E_LAUNCH, "svae_pose_expect: cannot reserve %zu bytes of LDS", lds);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ExpectGeo g{B, n_ref, M, rows, cols, C, A, S, A > 0 ? step : 0.0, inv_sigma2};
+    double* hn = static_cast<double*>(ws);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(expect_norms_kernel, dim3(n_ref), dim3(256), 0, st, ref, weight, rows * cols * C, C, hn);
+    hipLaunchKernelGGL(kernel, dim3(scratch ? dft_groups(B) : B), dim3(256), lds, st, y, ref, weight, log_prior,
+                       reinterpret_cast<const int*>(cand), pose_in, g, static_cast<const double*>(hn), contrib, cover_w, class_post,
+                       log_evidence, reinterpret_cast<int*>(best), scratch ? hn + roundup32((size_t)n_ref) : nullptr,
+                       (long)roundup32(expect_doubles(M, rows, cols, C, A, S)));
+    return launch_status("svae_pose_expect");
+}
+
+int svae_expect_sums_update(const double* contrib, const double* cover_w, const int32_t* cand, const int32_t* target, int32_t B,
+                            int32_t M, int32_t N, int32_t C, int32_t n_ref, int32_t n_classes, double* sum, double* count,
+                            svae_stream_t stream) {
+    if (B < 1 || N < 1 || C < 1 || C > SVAE_MAX_OUT || n_classes < 1 || n_classes > 4096 || n_ref < 1 || M < 1 || M > kExpectMaxSlots ||
+        (long)B * N * C > 0x7fffffffL || (long)n_classes * N * C > 0x7fffffffL || (long)B * M * N * C > 0x7fffffffL)
+        return fail(SVAE_E_INVALID, "svae_expect_sums_update: bad sizes B=%d M=%d N=%d C=%d n_ref=%d n_classes=%d (M in 1..%d)", B, M, N, C,
+                    n_ref, n_classes, kExpectMaxSlots);
+    if (!contrib || !cover_w || !cand || !sum || !count) return fail(SVAE_E_INVALID, "svae_expect_sums_update: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(expect_sums_update_kernel, dim3(blocks_for((long)n_classes * N)), dim3(256), 0, st, contrib, cover_w,
+                       reinterpret_cast<const int*>(cand), reinterpret_cast<const int*>(target), B, M, N, C, n_ref, n_classes, sum, count);
+    return launch_status("svae_expect_sums_update");
 }
 
 int svae_gemm_mode_set(int mode) {

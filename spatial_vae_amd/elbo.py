@@ -321,6 +321,29 @@ def classify_poses(y, rows, cols, ref, weight, cand, pose3, angles, step, shift,
     return picked, ops.pose_search(y, ref, weight, picked.ref_chosen, pose3, rows, cols, angles, step, shift, interp)
 
 
+@torch.no_grad()
+def expect_poses(y, rows, cols, ref, weight, cand, pose3, angles, step, shift, inv_sigma2, interp="bicubic", log_prior=None):
+    """The expectation step of maximum-likelihood class averaging for one minibatch (ops.pose_expect): each image spread over
+    the references its row of cand (B, M <= 64) int32 names and over classify_poses' neighbourhood of poses by its posterior under
+    Gaussian noise of variance 1 / inv_sigma2.  Returns ops.PoseExpect on the device, what ops.ClassSums.update_soft adds."""
+    return ops.pose_expect(y, ref, weight, log_prior, cand, pose3, rows, cols, angles, step, shift, inv_sigma2, interp)
+
+
+@torch.no_grad()
+def noise_sums(y, rows, cols, ref, weight, ref_index, pose3, rotate=True, translate=True, interp="bicubic"):
+    """What one minibatch adds to the noise estimate of a soft round, a (2) float64 device tensor: (sum over its labelled images,
+    pixels and channels of weight * cover * (aligned - ref[ref_index])^2 at the poses pose3, the same sum of weight * cover).
+    An image with ref_index < 0 adds nothing.  The round's sigma^2 is the ratio of the two, summed over the minibatches."""
+    aligned, cover = align_at(y, rows, cols, pose3, rotate, translate, interp)
+    B = y.size(0)
+    C = ref.numel() // (ref.size(0) * rows * cols)
+    on = ref_index >= 0
+    picked = ref.view(ref.size(0), rows * cols, C)[ref_index.clamp(min=0).long()]
+    w = weight.view(1, -1) * cover.double() * on.double().view(B, 1)
+    diff = aligned.view(B, rows * cols, C).double() - picked
+    return torch.stack([(w.unsqueeze(2) * diff * diff).sum(), w.sum() * C])
+
+
 def content_latents(per_image, q_mu, rotate, translate, pose="iw"):
     """The content part (B, z_dim) of the same estimate: what reconstruct_unposed decodes."""
     lay = row_layout(rotate, translate, q_mu.size(1))

@@ -37,6 +37,7 @@ INFER_MAX_REFINE_ROUNDS = 10
 INFER_MAX_REFINE_ANGLES = 32    # include/svae_refine.h's limits on A and S
 INFER_MAX_REFINE_SHIFT = 8
 INFER_MAX_REASSIGN_CLASSES = 4096   # include/svae_classify.h's limit on M (2K slots never arise: a half sees its own K averages)
+INFER_MAX_SOFT_CLASSES = 64         # include/svae_expect.h's limit on M
 
 
 def infer_arguments(argv=None):
@@ -135,10 +136,34 @@ def infer_arguments(argv=None):
                    "A class that loses every member has an all-zero average from then on, which the search skips: it stays empty")
     p.add_argument("--reassign_labels", metavar="PATH.npy", help="with --reassign: also write the final labels in the format "
                    "--labels reads")
+    p.add_argument("--refine_soft", action="store_true", help="with --refine --reassign: maximum-likelihood class averages.  Each "
+                   "round still names every image's best class and pose as --reassign does (labels, poses and --aligned keep their "
+                   "meaning), but the averages are accumulated softly: the image is spread over its best classes and over every "
+                   "rotation and shift of the search by its posterior probability under Gaussian noise, and added so weighted.  The "
+                   "class file's sum and count are then fractional")
+    p.add_argument("--refine_soft_classes", type=int, default=None, metavar="T", help="with --refine_soft: the classes an image is "
+                   "spread over, its T best of the round, 1..%d (default 8)" % INFER_MAX_SOFT_CLASSES)
+    p.add_argument("--refine_soft_sigma2", type=float, default=None, metavar="X", help="with --refine_soft: the noise variance per "
+                   "pixel, a finite X > 0 (default: estimated each round from the residuals of the images against the averages of "
+                   "their classes at their current poses)")
     args = p.parse_args(argv)
     args.train_argv = train_argv
     if args.reassign and args.refine is None:
         p.error("--reassign needs --refine")
+    if not args.refine_soft:
+        for name in ("refine_soft_classes", "refine_soft_sigma2"):
+            if vars(args)[name] is not None:
+                p.error("--%s needs --refine_soft" % name)
+    else:
+        if args.refine is None:
+            p.error("--refine_soft needs --refine")
+        if not args.reassign:
+            p.error("--refine_soft needs --reassign")
+        args.refine_soft_classes = 8 if args.refine_soft_classes is None else args.refine_soft_classes
+        if not 1 <= args.refine_soft_classes <= INFER_MAX_SOFT_CLASSES:
+            p.error("--refine_soft_classes must be in [1, %d] (got %d)" % (INFER_MAX_SOFT_CLASSES, args.refine_soft_classes))
+        if args.refine_soft_sigma2 is not None and not 0 < args.refine_soft_sigma2 < float("inf"):
+            p.error("--refine_soft_sigma2 must be a finite number > 0 (got %r)" % args.refine_soft_sigma2)
     if args.reassign_labels is not None:
         if not args.reassign:
             p.error("--reassign_labels needs --reassign")
@@ -653,7 +678,14 @@ def refine_walk(args, facts, split, acc, rows, lay):
     --reassign: the round scores each labelled image against all K references (under --frc the K of its own half: slot k holds
     2k + (i & 1)) with elbo.classify_poses, takes the winning slot as its label for this round's updates and the next round's
     search, and the pose refined against that winner.  An image with no live slot keeps label and pose.  The round's labels go
-    into a new tensor, swapped in at its end as the poses are."""
+    into a new tensor, swapped in at its end as the poses are.
+
+    --refine_soft: labels, poses and the aligned stack are made exactly as under --reassign, but the round's accumulators are
+    filled softly.  The image's T best slots by cand_score (a stable descending sort: ties keep slot order; a slot the search
+    skipped stays out) go through elbo.expect_poses, and ClassSums.update_soft adds the posterior-weighted rows: under --frc the
+    references are the 2K half averages, added as they are into the halves and folded reference r -> class r >> 1 into the full
+    sums.  The round's noise variance is --refine_soft_sigma2 or soft_sigma2's estimate; where its reciprocal is not positive and
+    finite the round runs hard and records nan."""
     n, m, bs, device = facts.n, facts.m, args.minibatch_size, acc.device
     A = args.refine_angles if facts.rotate else 0
     S = args.refine_shift if facts.translate else 0
@@ -676,8 +708,24 @@ def refine_walk(args, facts, split, acc, rows, lay):
                  "moved": torch.zeros(args.refine, dtype=torch.int64, device=device),
                  "class_score": torch.zeros(facts.images, K, dtype=torch.float64, device=device),
                  "margin": torch.zeros(facts.images, args.refine, dtype=torch.float64, device=device)}
+    soft = None
+    if args.refine_soft:
+        soft = {"sigma2": torch.full((args.refine,), float("nan"), dtype=torch.float64),
+                "log_evidence": torch.zeros(facts.images, args.refine, dtype=torch.float64, device=device),
+                "post_max": torch.zeros(facts.images, args.refine, dtype=torch.float64, device=device),
+                "class_post": torch.zeros(facts.images, K, dtype=torch.float64, device=device)}
+        T = min(K, args.refine_soft_classes)
+        fold = (torch.arange(2 * K, dtype=torch.int32, device=device) >> 1).contiguous() if args.frc else None
     for r in range(args.refine):
         ref = class_means(source)                   # a new tensor: the accumulators can be zeroed
+        inv_sigma2 = None
+        if soft is not None:
+            sigma2 = args.refine_soft_sigma2
+            if sigma2 is None:
+                sigma2 = soft_sigma2(args, facts, split, acc, ref, weight, label, pose)
+            if 0 < sigma2 < float("inf") and 0 < 1.0 / sigma2 < float("inf"):
+                inv_sigma2 = 1.0 / sigma2
+                soft["sigma2"][r] = sigma2
         for t in (acc.sums, acc.halves):
             if t is not None:
                 t.sum.zero_()
@@ -705,8 +753,25 @@ def refine_walk(args, facts, split, acc, rows, lay):
             new_pose[lo:hi] = found.pose
             score[lo:hi, r] = found.score
             offset[lo:hi, r] = found.offset
-            aligned = acc.update_at(lo, seen, found.pose, moved_to)
-            if r == args.refine - 1 and "aligned" in acc.stacks:
+            last = r == args.refine - 1
+            if inv_sigma2 is None:
+                aligned = acc.update_at(lo, seen, found.pose, moved_to)
+            else:
+                # the T best slots of the round, ties in slot order; a slot the search skipped (an emptied class) stays out
+                order = torch.sort(picked.cand_score, dim=1, descending=True, stable=True).indices[:, :T]
+                best_of = torch.where(picked.cand_score.gather(1, order) > float("-inf"), cand.gather(1, order), -1)
+                best_of = best_of.to(torch.int32).contiguous()
+                spread = E.expect_poses(seen, n, m, ref, weight, best_of, pose[lo:hi].contiguous(), A, step, S, inv_sigma2, acc.interp)
+                acc.sums.update_soft(spread, best_of, fold)
+                if acc.halves is not None:
+                    acc.halves.update_soft(spread, best_of)
+                soft["log_evidence"][lo:hi, r] = spread.log_evidence
+                soft["post_max"][lo:hi, r] = spread.class_post.max(1).values
+                if last:
+                    soft["class_post"][lo:hi] = torch.zeros_like(picked.cand_score).scatter_(1, order, spread.class_post)
+                if last and "aligned" in acc.stacks:
+                    aligned = E.align_at(seen, n, m, found.pose, acc.rotate, acc.translate, acc.interp)[0]
+            if last and "aligned" in acc.stacks:
                 acc.keep("aligned", lo, aligned)
         pose = new_pose
         if args.reassign:
@@ -716,6 +781,24 @@ def refine_walk(args, facts, split, acc, rows, lay):
     acc.refined = dict(before, pose=pose, score=score, offset=offset)
     if args.reassign:
         acc.refined.update(moves, label=label)
+    if soft is not None:
+        acc.refined["soft"] = soft
+
+
+def soft_sigma2(args, facts, split, acc, ref, weight, label, pose):
+    """--refine_soft's noise variance for the round about to start: over every labelled image at its current pose,
+    sum weight * cover * (aligned - ref[label])^2 over pixels and channels divided by sum weight * cover * C, the reference being
+    the one the image will be searched against (under --frc its own half's).  The two sums are accumulated in float64 on the
+    device over the minibatches in dataset order (elbo.noise_sums); the ratio is the one number read back, once per round,
+    because svae_pose_expect takes inv_sigma2 by value.  nan where nothing is labelled."""
+    bs = args.minibatch_size
+    sums = torch.zeros(2, dtype=torch.float64, device=acc.device)
+    for lo in range(0, facts.images, bs):
+        hi = min(lo + bs, facts.images)
+        ref_index = acc._half_labels(lo, hi, label[lo:hi]) if args.frc else label[lo:hi].contiguous()
+        sums += E.noise_sums(acc.seen(lo, split.data[lo:hi]), facts.n, facts.m, ref, weight, ref_index, pose[lo:hi].contiguous(),
+                             acc.rotate, acc.translate, acc.interp)
+    return float((sums[0] / sums[1]).item())
 
 
 def frc_finish(args, facts, acc):
@@ -772,6 +855,11 @@ def collect(args, facts, lay, rows, acc, fit, centres):
                           refine_label=acc.refined["labels"].cpu().numpy(), refine_moved=acc.refined["moved"].cpu().numpy(),
                           refine_class_score=acc.refined["class_score"].cpu().numpy(),
                           refine_class_margin=acc.refined["margin"].cpu().numpy())
+        if args.refine_soft:
+            soft = acc.refined["soft"]
+            meta.update(refine_soft=True, refine_soft_classes=args.refine_soft_classes, refine_soft_sigma2=args.refine_soft_sigma2)
+            arrays.update(refine_soft_sigma2=soft["sigma2"].numpy(), refine_log_evidence=soft["log_evidence"].cpu().numpy(),
+                          refine_post_max=soft["post_max"].cpu().numpy(), refine_class_post=soft["class_post"].cpu().numpy())
     found, labels = None, acc.labels
     if fit is not None:
         meta.update(pose=args.pose, cluster=args.cluster, cluster_out=args.cluster_out, cluster_labels=args.cluster_labels,
@@ -827,7 +915,9 @@ def class_arrays(args, facts, acc, labels):
     """The arrays of --class_averages: sums, counts, averages and members per class; under --ctf_correct wiener also the Wiener
     averages with their numerator and denominator (another lambda needs no second run); under --refine those of the last round,
     and average_unrefined from before the first; under --reassign members (and half_members) are those of the final labels, and
-    members_unrefined those of `labels`."""
+    members_unrefined those of `labels`.  Under --refine_soft sum and count (and half_sum, half_count) are fractional: the
+    posterior-weighted sums of the images over classes and poses, and of their coverage; members stays the count of the hard
+    labels."""
     n, m, sums = facts.n, facts.m, acc.sums
     shape = (sums.n_classes, n, m, facts.channels)
     total, count, average = _host_average(*sums.result(), shape)

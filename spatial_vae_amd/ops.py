@@ -53,7 +53,8 @@ _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib
                  for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES,
                                              **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES,
                                              **_lib.FRC_SIGNATURES, **_lib.REFINE_SIGNATURES,
-                                             **_lib.CLASSIFY_SIGNATURES, **_lib.GMM_SIGNATURES}.items()}
+                                             **_lib.CLASSIFY_SIGNATURES, **_lib.GMM_SIGNATURES,
+                                             **_lib.EXPECT_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -666,7 +667,8 @@ class ClassSums:
     """Per-class sums of aligned images (svae_class_sums_update): update() adds one minibatch -- aligned (B, N[, C]) and cover
     (B, N) or None as align_images returns them, label (B) int32 on the device, -1 = in no class --, result() gives (sum
     (n_classes, N, C), count (n_classes, N)), float64 on the device.  Images are added in the order they are handed over, without
-    atomics: the same sequence of updates gives the same bits."""
+    atomics: the same sequence of updates gives the same bits.  update_soft() adds posterior-weighted rows to the same
+    accumulators, which are fractional from then on."""
 
     def __init__(self, n_classes, N, C, device):
         device = torch.device(device)
@@ -691,6 +693,24 @@ class ClassSums:
             raise RuntimeError("ClassSums.update: aligned %s / cover %s do not hold %d images of %d pixels, %d channels"
                                % (tuple(aligned.shape), None if cover is None else tuple(cover.shape), B, self.N, self.C))
         _call("svae_class_sums_update", self.device, aligned, cover, label, B, self.N, self.C, self.n_classes, self.sum, self.count)
+
+    def update_soft(self, expect, cand, target=None):
+        """The soft counterpart of update() (svae_expect_sums_update, include/svae_expect.h): adds the contribution rows of
+        `expect` (a PoseExpect made for cand (B, M) int32) into the classes its references map to -- target (n_ref) int32 names
+        the class of each reference, None = the reference's own index -- in image order, then slot order, without atomics."""
+        for name, t in (("contrib", expect.contrib), ("cover_w", expect.cover_w), ("cand", cand), ("target", target)):
+            if t is not None:
+                _require_hip(t, name)
+        if cand.dtype != torch.int32 or cand.dim() != 2 or (target is not None and target.dtype != torch.int32):
+            raise RuntimeError("ClassSums.update_soft: cand must be (B, M) int32 and target int32")
+        B, M = cand.shape
+        if expect.contrib.dtype != torch.float64 or expect.cover_w.dtype != torch.float64 or \
+                expect.contrib.numel() != B * M * self.N * self.C or expect.cover_w.numel() != B * M * self.N:
+            raise RuntimeError("ClassSums.update_soft: contrib %s / cover_w %s do not hold %d x %d float64 rows of %d pixels, %d channels"
+                               % (tuple(expect.contrib.shape), tuple(expect.cover_w.shape), B, M, self.N, self.C))
+        n_ref = self.n_classes if target is None else target.numel()
+        _call("svae_expect_sums_update", self.device, expect.contrib, expect.cover_w, cand.contiguous(),
+              None if target is None else target.contiguous(), B, M, self.N, self.C, n_ref, self.n_classes, self.sum, self.count)
 
     def result(self):
         return self.sum, self.count
@@ -906,6 +926,55 @@ def pose_classify(y, ref, weight, cand, pose, rows, cols, angles, step, shift, i
     _call("svae_pose_classify", dev, yc, ref.contiguous(), weight, cand.contiguous(), pose.contiguous(), B, n_ref, M, rows, cols, C,
           A, float(step), S, _lib.ALIGN_INTERP[interp], choice, ref_chosen, cand_score, margin, ws, ws_bytes)
     return PoseClassify(choice, ref_chosen, cand_score, margin)
+
+
+PoseExpect = namedtuple("PoseExpect", "contrib cover_w class_post log_evidence best")
+
+
+def pose_expect(y, ref, weight, log_prior, cand, pose, rows, cols, angles, step, shift, inv_sigma2, interp="bicubic"):
+    """Each image spread over its candidate references and pose_search's neighbourhood by its posterior under Gaussian noise of
+    variance 1 / inv_sigma2 (svae_pose_expect, include/svae_expect.h): cand (B, M <= 64) int32 as pose_classify takes it (a
+    repeated reference is dead in its later slots), log_prior (n_ref) float64 or None (= 0), every other argument pose_classify's.
+    Returns PoseExpect(contrib (B, M, rows*cols, C) float64: the posterior-weighted sum of the image's shifted candidate planes
+    per slot; cover_w (B, M, rows*cols) float64: the same sum of their coverage; class_post (B, M) float64: the posterior of each
+    slot; log_evidence (B) float64; best (B, 4) int32 = slot, k, sx, sy of the largest log-weight, slot -1 for a skipped image)
+    on the device; nothing is read back."""
+    for name, t in (("y", y), ("ref", ref), ("cand", cand), ("pose", pose)):
+        _require_hip(t, name)
+    if interp not in _lib.ALIGN_INTERP:
+        raise RuntimeError("pose_expect: interp must be one of %s, got %r" % (sorted(_lib.ALIGN_INTERP), interp))
+    B, N = y.size(0), rows * cols
+    yc = _f32(y)
+    C = yc.numel() // (B * N) if B * N else 0
+    if C < 1 or C * B * N != yc.numel():
+        raise RuntimeError("pose_expect: y %s does not hold %d images of %dx%d" % (tuple(y.shape), B, rows, cols))
+    if ref.dtype != torch.float64 or ref.numel() % (N * C) or not ref.numel():
+        raise RuntimeError("pose_expect: ref %s (%s) must be float64 planes of %dx%dx%d" % (tuple(ref.shape), ref.dtype, rows, cols, C))
+    n_ref = ref.numel() // (N * C)
+    for name, t, n in (("weight", weight, N), ("log_prior", log_prior, n_ref)):
+        if t is not None:
+            _require_hip(t, name)
+            if t.dtype != torch.float64 or t.numel() != n:
+                raise RuntimeError("pose_expect: %s must be %d float64 values, got %s (%s)" % (name, n, tuple(t.shape), t.dtype))
+    weight = None if weight is None else weight.contiguous()
+    log_prior = None if log_prior is None else log_prior.contiguous()
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.size(0) != B or cand.size(1) < 1:
+        raise RuntimeError("pose_expect: cand must be (%d, M >= 1) int32, got %s (%s)" % (B, tuple(cand.shape), cand.dtype))
+    if pose.dtype != torch.float32 or tuple(pose.shape) != (B, 3):
+        raise RuntimeError("pose_expect: pose must be (%d, 3) float32, got %s (%s)" % (B, tuple(pose.shape), pose.dtype))
+    A, S, M = int(angles), int(shift), cand.size(1)
+    dev = y.device
+    contrib = torch.empty(B, M, N, C, dtype=torch.float64, device=dev)
+    cover_w = torch.empty(B, M, N, dtype=torch.float64, device=dev)
+    class_post = torch.empty(B, M, dtype=torch.float64, device=dev)
+    log_evidence = torch.empty(B, dtype=torch.float64, device=dev)
+    best = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    ws_bytes = _lib.lib().svae_pose_expect_workspace_bytes(B, n_ref, M, rows, cols, C, A, S)   # h, + slices above the LDS limit
+    ws = _buf(dev, ws_bytes, "expect")
+    _call("svae_pose_expect", dev, yc, ref.contiguous(), weight, log_prior, cand.contiguous(), pose.contiguous(), B, n_ref, M, rows,
+          cols, C, A, float(step), S, _lib.ALIGN_INTERP[interp], float(inv_sigma2), contrib, cover_w, class_post, log_evidence, best,
+          ws, ws_bytes)
+    return PoseExpect(contrib, cover_w, class_post, log_evidence, best)
 
 
 KMeansFit = namedtuple("KMeansFit", "label centres members record seed_index")
