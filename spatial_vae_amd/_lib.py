@@ -218,6 +218,16 @@ EXPECT_SIGNATURES = {
 }
 
 
+# ---- include/svae_pca.h: principal axes of the content latents, an eleventh header with a table of its own ----
+# Same rules (tests/test_pca_cpu.py holds these rows to that header's prototypes).  The header adds no constant and no struct.
+PCA_SIGNATURES = {
+    "svae_pca_workspace_bytes": (sz, [i64, i32, i32]),
+    "svae_pca_moments": (cint, [vp, i64, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "svae_pca_eigen": (cint, [vp, i32, i32, vp, vp, vp, vp, vp]),
+    "svae_pca_project": (cint, [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -242,7 +252,8 @@ def lib():
     L = ctypes.CDLL(path)
     for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES,
                                       **CLUSTER_SIGNATURES, **FRC_SIGNATURES, **REFINE_SIGNATURES,
-                                      **CLASSIFY_SIGNATURES, **GMM_SIGNATURES, **EXPECT_SIGNATURES}.items():
+                                      **CLASSIFY_SIGNATURES, **GMM_SIGNATURES, **EXPECT_SIGNATURES,
+                                      **PCA_SIGNATURES}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

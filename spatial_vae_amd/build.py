@@ -19,7 +19,7 @@ def _stale():
     deps = [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(_HERE, "..", "include", h)
                                                          for h in ("svae.h", "svae_stream.h", "svae_align.h", "svae_ctfcorr.h",
                                                                    "svae_cluster.h", "svae_frc.h", "svae_refine.h",
-                                                                   "svae_classify.h", "svae_gmm.h", "svae_expect.h")]
+                                                                   "svae_classify.h", "svae_gmm.h", "svae_expect.h", "svae_pca.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

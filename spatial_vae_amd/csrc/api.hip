@@ -21,6 +21,7 @@
 #include "../../include/svae_refine.h"
 #include "../../include/svae_classify.h"
 #include "../../include/svae_gmm.h"
+#include "../../include/svae_pca.h"
 #include "../../include/svae_expect.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
@@ -34,6 +35,7 @@
 #include "classify.h"
 #include "cluster.h"
 #include "gmm.h"
+#include "pca.h"
 #include "expect.h"
 #include "encoder.h"
 #include "split.h"
@@ -2181,6 +2183,71 @@ int svae_gmm_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t updat
     hipLaunchKernelGGL(gmm_tail_kernel, dim3(update ? blocks_for((long)k * (D + 1)) : 1), dim3(256), 0, st, D, k, chunks,
                        update ? (int)kGmmStep : (int)kGmmLabelOnly, reg, tol, weight, mean, var, rec, w);
     return launch_status("svae_gmm_step");
+}
+
+// ---- principal axes of the content latents (include/svae_pca.h) ----
+size_t svae_pca_workspace_bytes(int64_t N, int32_t D, int32_t G) {
+    if (!pca_sizes_ok(N, D, G)) return 0;
+    return pca_ws_words((long)N, D, G) * 8;
+}
+
+int svae_pca_moments(const float* x, int64_t N, int32_t D, int32_t G, const int32_t* group, int64_t* count, double* mean,
+                     double* cov, void* ws, size_t ws_bytes, svae_stream_t stream) {
+    if (!x || !count || !mean || !cov) return fail(SVAE_E_INVALID, "svae_pca_moments: null x, count, mean or cov");
+    if (misaligned8(count) || misaligned8(mean) || misaligned8(cov))
+        return fail(SVAE_E_INVALID, "svae_pca_moments: count, mean and cov must be 8-byte aligned");
+    if (!pca_sizes_ok(N, D, G))
+        return fail(SVAE_E_INVALID, "svae_pca_moments: bad sizes N=%lld D=%d G=%d (1 <= D <= %d, 1 <= G <= %d, G D (D + 1) / 2 <= %d, "
+                    "1 <= N < 2^31)", (long long)N, D, G, kKmeansMaxD, kPcaMaxG, kPcaMaxPartials);
+    if (!group && G != 1) return fail(SVAE_E_INVALID, "svae_pca_moments: a null group needs G == 1 (got %d)", G);
+    if (!ws) return fail(SVAE_E_WORKSPACE, "svae_pca_moments: null workspace");
+    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(SVAE_E_WORKSPACE, "svae_pca_moments: workspace not 256-byte aligned");
+    const size_t need = pca_ws_words((long)N, D, G) * 8;
+    if (ws_bytes < need) return fail(SVAE_E_WORKSPACE, "svae_pca_moments: workspace too small: %zu < %zu", ws_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long P = kmeans_chunk((long)N);
+    const int chunks = (int)(((long)N + P - 1) / P);
+    const PcaWs w = pca_ws(ws, (long)N, D, G);
+    long long* cnt = reinterpret_cast<long long*>(count);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(pca_sums_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, G, P, reinterpret_cast<const int*>(group), w);
+    hipLaunchKernelGGL(pca_mean_kernel, dim3(blocks_for((long)G * (D + 1))), dim3(256), 0, st, D, G, chunks, cnt, mean, w);
+    hipLaunchKernelGGL(pca_products_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, G, P, static_cast<const double*>(mean), w);
+    hipLaunchKernelGGL(pca_cov_kernel, dim3(blocks_for((long)G * (D * (D + 1) / 2))), dim3(256), 0, st, D, G, chunks,
+                       static_cast<const long long*>(cnt), cov, w);
+    return launch_status("svae_pca_moments");
+}
+
+int svae_pca_eigen(const double* cov, int32_t D, int32_t G, double* eigenvalues, double* components, int32_t* sweeps,
+                   double* off_norm, svae_stream_t stream) {
+    if (!cov || !eigenvalues || !components || !sweeps || !off_norm)
+        return fail(SVAE_E_INVALID, "svae_pca_eigen: null cov, eigenvalues, components, sweeps or off_norm");
+    if (misaligned8(cov) || misaligned8(eigenvalues) || misaligned8(components) || misaligned8(off_norm))
+        return fail(SVAE_E_INVALID, "svae_pca_eigen: cov, eigenvalues, components and off_norm must be 8-byte aligned");
+    if (!pca_sizes_ok(1, D, G))
+        return fail(SVAE_E_INVALID, "svae_pca_eigen: bad sizes D=%d G=%d (1 <= D <= %d, 1 <= G <= %d, G D (D + 1) / 2 <= %d)", D, G,
+                    kKmeansMaxD, kPcaMaxG, kPcaMaxPartials);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(pca_eigen_kernel, dim3(G), dim3(256), 0, st, cov, D, eigenvalues, components, reinterpret_cast<int*>(sweeps), off_norm);
+    return launch_status("svae_pca_eigen");
+}
+
+int svae_pca_project(const float* x, int64_t N, int32_t D, int32_t G, int32_t P, const int32_t* group, const int64_t* count,
+                     const double* mean, const double* components, double* proj, svae_stream_t stream) {
+    if (!x || !count || !mean || !components || !proj) return fail(SVAE_E_INVALID, "svae_pca_project: null x, count, mean, components or proj");
+    if (misaligned8(count) || misaligned8(mean) || misaligned8(components) || misaligned8(proj))
+        return fail(SVAE_E_INVALID, "svae_pca_project: count, mean, components and proj must be 8-byte aligned");
+    if (!pca_sizes_ok(N, D, G))
+        return fail(SVAE_E_INVALID, "svae_pca_project: bad sizes N=%lld D=%d G=%d (1 <= D <= %d, 1 <= G <= %d, G D (D + 1) / 2 <= %d, "
+                    "1 <= N < 2^31)", (long long)N, D, G, kKmeansMaxD, kPcaMaxG, kPcaMaxPartials);
+    if (P < 1 || P > D) return fail(SVAE_E_INVALID, "svae_pca_project: P = %d must be in 1..D = %d", P, D);
+    if (!group && G != 1) return fail(SVAE_E_INVALID, "svae_pca_project: a null group needs G == 1 (got %d)", G);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(pca_project_kernel, dim3(blocks_for((long)N * P)), dim3(256), 0, st, x, (long)N, D, G, P,
+                       reinterpret_cast<const int*>(group), reinterpret_cast<const long long*>(count), mean, components, proj);
+    return launch_status("svae_pca_project");
 }
 
 // ---- maximum-likelihood class averages (include/svae_expect.h) ----

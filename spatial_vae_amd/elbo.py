@@ -386,6 +386,36 @@ def mixture_latents(points, kmeans_fit, iters, reg=1e-6, tol=1e-8, min_resp=0.0)
     return out
 
 
+def principal_axes(points, label=None, n_classes=None, components=None):
+    """The principal axes of the content latents `points` (N, D) on the device (ops.LatentPCA): of all of them (label None: one
+    group), or of each of the n_classes classes of `label` (N) int32, -1 or any entry outside [0, n_classes) = in no class.
+    components: the columns of "projections" (default D).  Returns the PcaFit's device tensors by name, each with a leading
+    group axis -- "count", "mean", "cov", "eigenvalues", "components" (rows are axes), "sweeps", "off_norm" -- with "projections"
+    (N, components): each point along the axes of its own group, and "explained_variance_ratio" = eigenvalues / their sum, 0
+    where the sum is 0.  Nothing is read back."""
+    points = points.float().contiguous()
+    G = 1 if label is None else int(n_classes)
+    fit = ops.LatentPCA(points.size(1), points.device).fit(points, None if label is None else label.to(torch.int32).contiguous(), G,
+                                                           components)
+    out = dict(fit._asdict())
+    out["projections"] = out.pop("proj")
+    total = fit.eigenvalues.sum(1, keepdim=True)
+    out["explained_variance_ratio"] = torch.where(total != 0, fit.eigenvalues / total, torch.zeros_like(fit.eigenvalues))
+    return out
+
+
+def traverse_latents(mean, eigenvalues, components, axes, steps, span):
+    """Walks along the first `axes` principal axes: z[..., p, s + steps, :] = mean + (s / steps) * span * sqrt(max(lambda_p, 0))
+    * v_p for s = -steps..steps, with mean (..., D), eigenvalues (..., D) and components (..., D, D) as principal_axes returns
+    them (any leading axes).  Formed in double where the inputs live, rounded to float once: (..., axes, 2 steps + 1, D) fp32."""
+    axes, steps = int(axes), int(steps)
+    mean, lam, v = mean.double(), eigenvalues.double()[..., :axes], components.double()[..., :axes, :]
+    frac = torch.arange(-steps, steps + 1, dtype=torch.float64, device=mean.device) / steps
+    reach = (frac * float(span)).unsqueeze(0) * torch.sqrt(torch.clamp(lam, min=0.0)).unsqueeze(-1)     # (..., axes, frames)
+    z = mean[..., None, None, :] + reach.unsqueeze(-1) * v.unsqueeze(-2)
+    return z.float()
+
+
 def ring_layout(n, m):
     """The rings of an n x m plane (include/svae_frc.h): (L, R, ring_frequency) with L = min(n, m), R = L // 2 + 1 rings and
     ring r standing for ring_frequency[r] = r / L cycles per pixel."""

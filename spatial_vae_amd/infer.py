@@ -2,11 +2,12 @@
 
 Its own command line (infer_arguments: every refusal that needs no data, made before the kernel library is loaded), its file
 writers, and infer_main: a short sequence of stages -- load the model, check the request against the split, allocate the
-accumulators, walk the minibatches scoring (and aligning) them, cluster, refine the poses against the class averages (--refine;
+accumulators, walk the minibatches scoring (and aligning) them, cluster, take the principal axes of the content latents (--pca),
+refine the poses against the class averages (--refine;
 with --reassign also the classes),
 finish the half-set correlation (--frc), collect and
-write.  The device work is elbo.py's (score_minibatch, align_minibatch, reconstruct_unposed, cluster_latents, refine_poses,
-classify_poses, frc_weight) and ops.py's.
+write.  The device work is elbo.py's (score_minibatch, align_minibatch, reconstruct_unposed, cluster_latents, principal_axes,
+traverse_latents, refine_poses, classify_poses, frc_weight) and ops.py's.
 """
 import collections
 import json
@@ -38,6 +39,9 @@ INFER_MAX_REFINE_ANGLES = 32    # include/svae_refine.h's limits on A and S
 INFER_MAX_REFINE_SHIFT = 8
 INFER_MAX_REASSIGN_CLASSES = 4096   # include/svae_classify.h's limit on M (2K slots never arise: a half sees its own K averages)
 INFER_MAX_SOFT_CLASSES = 64         # include/svae_expect.h's limit on M
+INFER_MAX_PCA_STEPS = 50
+INFER_MAX_PCA_PARTIALS = 32768      # include/svae_pca.h's limit on G D (D + 1) / 2
+PCA_KEYS = ("count", "mean", "cov", "eigenvalues", "components", "explained_variance_ratio", "projections", "sweeps", "off_norm")
 
 
 def infer_arguments(argv=None):
@@ -110,6 +114,20 @@ def infer_arguments(argv=None):
                    "iteration gains no more than X |log-likelihood|, X >= 0 (default 1e-8, a convention too)")
     p.add_argument("--cluster_min_resp", type=float, default=None, metavar="P", help="with --cluster_gmm: an image whose largest "
                    "responsibility is below P, 0 <= P < 1, is in no class (label -1; default 0, a convention too: every image stays)")
+    p.add_argument("--pca", metavar="PATH.npz", help="also write the principal axes of the split's content latents (--pose selects "
+                   "whose: z_iw, z_best or z_q), found on the device: mean, covariance, eigenvalues, components (rows are axes), "
+                   "explained variance ratio and every image's projections")
+    p.add_argument("--pca_components", type=int, default=None, metavar="P", help="with --pca: the columns of projections, 1..z_dim "
+                   "(default z_dim)")
+    p.add_argument("--pca_traverse", type=int, default=None, metavar="Q", help="with --pca: also decode a walk along each of the first "
+                   "Q axes, 0..z_dim (default 0): traverse_latents and traverse_images")
+    p.add_argument("--pca_steps", type=int, default=None, metavar="T", help="with --pca_traverse: steps on each side of the mean, "
+                   "1..%d (default 5: 2 T + 1 frames)" % INFER_MAX_PCA_STEPS)
+    p.add_argument("--pca_span", type=float, default=None, metavar="X", help="with --pca_traverse: how far the walk reaches on each "
+                   "side, in standard deviations along the axis, a finite X > 0 (default 2.0)")
+    p.add_argument("--pca_per_class", action="store_true", help="with --pca and --cluster: also the principal axes of every class "
+                   "(the arrays prefixed class_), under the labels the class averages are built from; a walk starts from the "
+                   "class's mean along the class's own axes")
     p.add_argument("--frc", action="store_true", help="with --class_averages: also accumulate each class over two disjoint halves "
                    "(image i of the split in half i & 1) and add their sums, the Fourier ring correlation of the two half averages, "
                    "the resolution at the 0.143 and 0.5 thresholds and the full average filtered by sqrt(2 FRC / (1 + FRC)).  One "
@@ -241,6 +259,28 @@ def infer_arguments(argv=None):
             p.error("--cluster_gmm_tol must be a finite number >= 0 (got %r)" % args.cluster_gmm_tol)
         if not 0 <= args.cluster_min_resp < 1:
             p.error("--cluster_min_resp must be in [0, 1) (got %r)" % args.cluster_min_resp)
+    if args.pca is None:
+        for name in ("pca_components", "pca_traverse", "pca_steps", "pca_span"):
+            if vars(args)[name] is not None:
+                p.error("--%s needs --pca" % name)
+        if args.pca_per_class:
+            p.error("--pca_per_class needs --pca")
+    else:
+        if os.path.splitext(args.pca)[1] != ".npz":
+            p.error("--pca must end in .npz (got %s)" % args.pca)
+        if args.pca_per_class and args.cluster is None:
+            p.error("--pca_per_class needs --cluster")
+        args.pca_traverse = 0 if args.pca_traverse is None else args.pca_traverse
+        args.pca_steps = 5 if args.pca_steps is None else args.pca_steps
+        args.pca_span = 2.0 if args.pca_span is None else args.pca_span
+        if args.pca_components is not None and args.pca_components < 1:
+            p.error("--pca_components must be >= 1 (got %d)" % args.pca_components)
+        if args.pca_traverse < 0:
+            p.error("--pca_traverse must be >= 0 (got %d)" % args.pca_traverse)
+        if not 1 <= args.pca_steps <= INFER_MAX_PCA_STEPS:
+            p.error("--pca_steps must be in [1, %d] (got %d)" % (INFER_MAX_PCA_STEPS, args.pca_steps))
+        if not 0 < args.pca_span < float("inf"):
+            p.error("--pca_span must be a finite number > 0 (got %r)" % args.pca_span)
     if args.ctf_correct is not None and args.script != "particles":
         p.error("--ctf_correct is for particles (the script whose images have a CTF), not %s" % args.script)
     if args.ctf_correct == "flip" and args.aligned is None and args.class_averages is None:
@@ -282,7 +322,7 @@ def infer_arguments(argv=None):
         p.error("--labels needs --class_averages")
     if args.aligned is None and args.recon is None and args.class_averages is None:
         for name in ("pose", "interp"):
-            if vars(args)[name] is not None and not (name == "pose" and args.cluster is not None):
+            if vars(args)[name] is not None and not (name == "pose" and (args.cluster is not None or args.pca is not None)):
                 p.error("--%s needs one of --aligned, --recon, --class_averages" % name)
     args.pose, args.interp = args.pose or "iw", args.interp or "bicubic"
     args.label_array = None
@@ -478,6 +518,19 @@ def check_request(args, facts):
         if args.cluster_gmm is not None and images * args.cluster > INFER_MAX_GMM_RESP:
             _refuse("--cluster_gmm keeps a responsibility per image and class: {} images x {} classes exceed 2^28".format(
                 images, args.cluster))
+    if args.pca is not None:
+        z_dim = E.row_layout(facts.rotate, facts.translate, facts.inf_dim).z_dim
+        if z_dim < 1:
+            _refuse("--pca takes the axes of the content latents, and this model has none (z_dim = 0)")
+        if images < 1:
+            _refuse("--pca: the {} split has no image".format(facts.split))
+        if args.pca_components is not None and args.pca_components > z_dim:
+            _refuse("--pca_components must be in [1, {0}], this model's z_dim (got {1})".format(z_dim, args.pca_components))
+        if args.pca_traverse > z_dim:
+            _refuse("--pca_traverse must be in [0, {0}], this model's z_dim (got {1})".format(z_dim, args.pca_traverse))
+        if args.pca_per_class and args.cluster * (z_dim * (z_dim + 1) // 2) > INFER_MAX_PCA_PARTIALS:
+            _refuse("--pca_per_class keeps z_dim (z_dim + 1) / 2 products per class: {} classes x {} exceed {}".format(
+                args.cluster, z_dim * (z_dim + 1) // 2, INFER_MAX_PCA_PARTIALS))
     if args.refine is not None:
         if not facts.rotate and not facts.translate:
             _refuse("--refine searches rotations and shifts, and this model infers neither")
@@ -659,6 +712,52 @@ def cluster_walk(args, model, split, acc, rows, lay):
     return fit, centres
 
 
+def pca_walk(args, model, split, acc, rows, lay):
+    """--pca: the principal axes of every image's content latents (elbo.principal_axes on what cluster_walk clusters), under
+    --pca_per_class also those of every class under acc.label_d, the labels the later stages see.  With --pca_traverse the walks
+    of elbo.traverse_latents -- from the global mean along the global axes, and from each class's mean along that class's own --
+    go through the decoder's un-posed reconstruction in one call.  Returns {"global": ..., "class": ... or None,
+    "traverse_latents", "traverse_images", "class_traverse_latents", "class_traverse_images" where asked for}, all on the
+    device: nothing is read back."""
+    per_image, q_mu, _ = split_rows(torch.cat(rows), lay)
+    zc = E.content_latents(per_image, q_mu, model.cfg["rotate"], model.cfg["translate"], args.pose)
+    found = {"global": E.principal_axes(zc, components=args.pca_components), "class": None}
+    if args.pca_per_class:
+        found["class"] = E.principal_axes(zc, acc.label_d, args.cluster, args.pca_components)
+    if args.pca_traverse > 0:
+        walks = [(name, E.traverse_latents(fit["mean"], fit["eigenvalues"], fit["components"], args.pca_traverse, args.pca_steps,
+                                           args.pca_span))
+                 for name, fit in (("", found["global"]), ("class_", found["class"])) if fit is not None]
+        z = torch.cat([w.reshape(-1, zc.size(1)) for _, w in walks])
+        images = E.reconstruct_unposed(split.x, model.p_net, z.size(0), z, gaussian_mean=(args.script == "particles"))
+        lo = 0
+        for name, w in walks:
+            n = w.numel() // zc.size(1)
+            found[name + "traverse_latents"], found[name + "traverse_images"] = w, images[lo:lo + n]
+            lo += n
+    return found
+
+
+def pca_arrays(args, facts, found, meta):
+    """The arrays of the --pca file, transferred once: the global fit without its group axis, the walks, under --pca_per_class
+    the same arrays prefixed class_ with a leading class axis (class_projections: each image in its own class's basis)."""
+    out = {}
+    for prefix, fit in (("", found["global"]), ("class_", found["class"])):
+        if fit is None:
+            continue
+        for key in PCA_KEYS:
+            a = fit[key].cpu().numpy()
+            out[prefix + key] = a[0] if not prefix and key != "projections" else a
+        for key in ("traverse_latents", "traverse_images"):
+            if prefix + key in found:
+                a = found[prefix + key].cpu().numpy()
+                lead = (args.cluster,) if prefix else ()    # the walks of the global fit carry its group axis of 1: dropped
+                frames = (args.pca_traverse, 2 * args.pca_steps + 1)
+                out[prefix + key] = a.reshape(lead + frames + ((facts.n, facts.m, -1) if key == "traverse_images" else (-1,)))
+    out["meta"] = np.array(json.dumps(meta))
+    return out
+
+
 def class_means(sums):
     """sum / count of a ClassSums where the count is positive and 0 elsewhere, (n_classes, N, C) float64 on the device."""
     total, count = sums.result()
@@ -827,9 +926,10 @@ def frc_finish(args, facts, acc):
                "frc_weight": weight.view(K, channels, -1), "average_filtered": filtered.view(K, channels, n, m).permute(0, 2, 3, 1)}
 
 
-def collect(args, facts, lay, rows, acc, fit, centres):
+def collect(args, facts, lay, rows, acc, fit, centres, axes=None):
     """The one transfer of the scores (and the one synchronisation, when stacks were filled) and what the files will hold:
-    (the score file's arrays, the --cluster_out arrays or None, the host labels of the classes, the summary line)."""
+    (the score file's arrays, the --cluster_out arrays or None, the host labels of the classes, the summary line, the --pca
+    arrays or None)."""
     host = torch.cat(rows).cpu().numpy()
     if acc.stacks:
         torch.cuda.synchronize(acc.device)          # every minibatch's copy has landed
@@ -877,10 +977,15 @@ def collect(args, facts, lay, rows, acc, fit, centres):
             found.update(mixture_arrays(args, facts, fit))
             labels = found["gmm_label_used"]
         found["meta"] = np.array(json.dumps(meta))
+    pca = None
+    if axes is not None:                            # after the cluster file's meta: that file stays what it was
+        meta.update(pca=args.pca, pca_pose=args.pose, pca_components=args.pca_components, pca_traverse=args.pca_traverse,
+                    pca_steps=args.pca_steps, pca_span=args.pca_span, pca_per_class=args.pca_per_class)
+        pca = pca_arrays(args, facts, axes, meta)
     arrays["meta"] = np.array(json.dumps(meta))
     summary = "images {}\tbound {!r}\tlog p(x|z) {!r}\tKL {!r}\tmedian ESS {:.3f}".format(
         host.shape[0], means[0], means[1], means[2], float(np.median(arrays["ess"])))
-    return arrays, found, labels, summary
+    return arrays, found, labels, summary, pca
 
 
 def mixture_arrays(args, facts, fit):
@@ -966,8 +1071,9 @@ def frc_arrays(args, facts, acc, labels):
     return out
 
 
-def write_outputs(args, facts, acc, arrays, found, labels):
-    """The files, each written atomically: the stacks, the class averages, the cluster file and its labels, the score file last."""
+def write_outputs(args, facts, acc, arrays, found, labels, pca=None):
+    """The files, each written atomically: the stacks, the class averages, the cluster file and its labels, the --pca file, the
+    score file last."""
     for k, stack in acc.stacks.items():
         write_stack(vars(args)[k], stack.numpy().reshape(facts.images, facts.n, facts.m, facts.channels))
     if acc.sums is not None:
@@ -978,6 +1084,8 @@ def write_outputs(args, facts, acc, arrays, found, labels):
             write_atomically(args.cluster_labels, lambda f: np.save(f, labels))
     if args.reassign_labels is not None:
         write_atomically(args.reassign_labels, lambda f: np.save(f, arrays["label_refined"]))
+    if pca is not None:
+        write_npz(args.pca, pca)
     write_npz(args.out, arrays)
 
 
@@ -992,11 +1100,12 @@ def infer_main(args, parser_fn, build, positional=()):
     acc = Accumulators(args, facts, model.cfg, model.device)
     rows = score_walk(args, model, split, acc)
     fit, centres = cluster_walk(args, model, split, acc, rows, lay) if args.cluster is not None else (None, None)
+    axes = pca_walk(args, model, split, acc, rows, lay) if args.pca is not None else None
     if args.refine is not None:
         refine_walk(args, facts, split, acc, rows, lay)
     if args.frc:
         frc_finish(args, facts, acc)
-    arrays, found, labels, summary = collect(args, facts, lay, rows, acc, fit, centres)
-    write_outputs(args, facts, acc, arrays, found, labels)
+    arrays, found, labels, summary, pca = collect(args, facts, lay, rows, acc, fit, centres, axes)
+    write_outputs(args, facts, acc, arrays, found, labels, pca)
     print(summary)
     return 0

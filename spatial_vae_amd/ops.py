@@ -54,7 +54,7 @@ _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib
                                              **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES,
                                              **_lib.FRC_SIGNATURES, **_lib.REFINE_SIGNATURES,
                                              **_lib.CLASSIFY_SIGNATURES, **_lib.GMM_SIGNATURES,
-                                             **_lib.EXPECT_SIGNATURES}.items()}
+                                             **_lib.EXPECT_SIGNATURES, **_lib.PCA_SIGNATURES}.items()}
 
 
 def _call(name, device, *args):
@@ -1108,6 +1108,64 @@ class GaussianMixture:
         ctypes.memmove(ctypes.byref(rec), record.cpu().numpy().tobytes(), ctypes.sizeof(rec))
         out = {name: int(getattr(rec, name)) for name, _ in _lib.GmmRecord._fields_[:4]}
         out.update(loglik=float(rec.loglik), previous=float(rec.previous))
+        return out
+
+
+PcaFit = namedtuple("PcaFit", "count mean cov eigenvalues components sweeps off_norm proj")
+
+
+class LatentPCA:
+    """The principal axes of (N, D) fp32 points on the device, globally or per group (include/svae_pca.h): mean and covariance
+    in two ordered passes, cyclic Jacobi per covariance, every point's coordinates along its group's axes.  Every sum and
+    rotation has a fixed order and nothing is atomic, so the same inputs give the same bits; nothing is read back."""
+
+    MAX_GROUPS = 1024
+    MAX_PARTIALS = 32768        # G * D (D + 1) / 2
+
+    def __init__(self, D, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("spatial_vae_amd: LatentPCA must live on a HIP device (got %s); the MI355X path has no CPU "
+                               "fallback" % device)
+        self.D, self.device = int(D), device
+        if not 1 <= self.D <= 64:
+            raise RuntimeError("LatentPCA: D = %d must be in 1..64" % self.D)
+
+    @classmethod
+    def max_groups(cls, D):
+        """The most groups one call takes for points of D coordinates."""
+        return min(cls.MAX_GROUPS, cls.MAX_PARTIALS // (D * (D + 1) // 2))
+
+    def fit(self, points, group=None, G=1, P=None):
+        """svae_pca_moments, svae_pca_eigen and svae_pca_project, enqueued on the current stream.  points: (N, D) fp32 contiguous
+        on the device; group: (N) int32 on the device with entries in [0, G) (any other entry: in no group), or None with G == 1;
+        P: the columns of proj, 1..D (default D).  Returns PcaFit of device tensors: count (G) int64, mean (G, D), cov (G, D, D),
+        eigenvalues (G, D) descending, components (G, D, D) with rows as axes, sweeps (G) int32, off_norm (G) and proj (N, P)."""
+        _require_hip(points, "points")
+        if points.dtype != torch.float32 or points.dim() != 2 or points.size(1) != self.D or not points.is_contiguous():
+            raise RuntimeError("LatentPCA.fit: points must be a contiguous (N, %d) float32 tensor, got %s %s"
+                               % (self.D, tuple(points.shape), points.dtype))
+        N, D, G, dev = points.size(0), self.D, int(G), self.device
+        P = D if P is None else int(P)
+        if not 1 <= P <= D:
+            raise RuntimeError("LatentPCA.fit: P = %d must be in 1..%d" % (P, D))
+        if group is None:
+            if G != 1:
+                raise RuntimeError("LatentPCA.fit: without a group tensor G must be 1 (got %d)" % G)
+        elif not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (N,) or not group.is_cuda:
+            raise RuntimeError("LatentPCA.fit: group must be %d int32 numbers on the device" % N)
+        ws_bytes = _lib.lib().svae_pca_workspace_bytes(N, D, G)
+        if ws_bytes == 0:
+            raise RuntimeError("LatentPCA.fit: bad geometry N = %d, D = %d, G = %d (G D (D + 1) / 2 <= %d)" % (N, D, G, self.MAX_PARTIALS))
+        ws = _buf(dev, ws_bytes, "pca")
+        group = None if group is None else group.contiguous()
+        f64 = dict(dtype=torch.float64, device=dev)
+        out = PcaFit(torch.empty(G, dtype=torch.int64, device=dev), torch.empty(G, D, **f64), torch.empty(G, D, D, **f64),
+                     torch.empty(G, D, **f64), torch.empty(G, D, D, **f64), torch.empty(G, dtype=torch.int32, device=dev),
+                     torch.empty(G, **f64), torch.empty(N, P, **f64))
+        _call("svae_pca_moments", dev, points, N, D, G, group, out.count, out.mean, out.cov, ws, ws.numel())
+        _call("svae_pca_eigen", dev, out.cov, D, G, out.eigenvalues, out.components, out.sweeps, out.off_norm)
+        _call("svae_pca_project", dev, points, N, D, G, P, group, out.count, out.mean, out.components, out.proj)
         return out
 
 
