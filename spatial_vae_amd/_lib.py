@@ -228,6 +228,17 @@ PCA_SIGNATURES = {
 }
 
 
+# ---- the one list of the headers of include/, in the order they were added: header -> its table above ----
+# lib(), ops._POINTER_ARGS, build.dependencies() and __graft_entry__.build() walk it; a twelfth header is one more row.
+HEADERS = {
+    "svae.h": SIGNATURES, "svae_stream.h": STREAM_SIGNATURES, "svae_align.h": ALIGN_SIGNATURES,
+    "svae_ctfcorr.h": CTFCORR_SIGNATURES, "svae_cluster.h": CLUSTER_SIGNATURES, "svae_frc.h": FRC_SIGNATURES,
+    "svae_refine.h": REFINE_SIGNATURES, "svae_classify.h": CLASSIFY_SIGNATURES, "svae_gmm.h": GMM_SIGNATURES,
+    "svae_expect.h": EXPECT_SIGNATURES, "svae_pca.h": PCA_SIGNATURES,
+}
+ALL_SIGNATURES = {name: row for table in HEADERS.values() for name, row in table.items()}
+
+
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
     import)."""
@@ -250,10 +261,7 @@ def lib():
         raise RuntimeError("spatial_vae_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
-    for name, (restype, argtypes) in {**SIGNATURES, **STREAM_SIGNATURES, **ALIGN_SIGNATURES, **CTFCORR_SIGNATURES,
-                                      **CLUSTER_SIGNATURES, **FRC_SIGNATURES, **REFINE_SIGNATURES,
-                                      **CLASSIFY_SIGNATURES, **GMM_SIGNATURES, **EXPECT_SIGNATURES,
-                                      **PCA_SIGNATURES}.items():
+    for name, (restype, argtypes) in ALL_SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

@@ -12,15 +12,17 @@ def library_path():
     return _LIB
 
 
+def dependencies():
+    """Every file the library is built from: csrc/ and the headers of include/ that _lib.HEADERS lists."""
+    from ._lib import HEADERS   # not at import: _lib imports this module
+    return [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(_HERE, "..", "include", h) for h in HEADERS]
+
+
 def _stale():
     if not os.path.exists(_LIB):
         return True
     t = os.path.getmtime(_LIB)
-    deps = [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(_HERE, "..", "include", h)
-                                                         for h in ("svae.h", "svae_stream.h", "svae_align.h", "svae_ctfcorr.h",
-                                                                   "svae_cluster.h", "svae_frc.h", "svae_refine.h",
-                                                                   "svae_classify.h", "svae_gmm.h", "svae_expect.h", "svae_pca.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in dependencies())
 
 
 def build(force=False, verbose=False):

@@ -1710,626 +1710,11 @@ int svae_rotate_bicubic(const float* y, float* y_rot, const double* matrix, cons
     return launch_status("svae_rotate_bicubic");
 }
 
-// ---- alignment into the canonical frame and class sums (include/svae_align.h) ----
-int svae_align_images(const float* y, const float* theta, const float* dx, int32_t B, int32_t rows, int32_t cols, int32_t C,
-                      int32_t interp, float* aligned, uint8_t* cover, svae_stream_t stream) {
-    if (B < 1 || rows < 2 || cols < 2 || C < 1 || C > SVAE_MAX_OUT || (long)B * rows * cols * C > 0x7fffffffL)
-        return fail(SVAE_E_INVALID, "svae_align_images: bad sizes B=%d rows=%d cols=%d C=%d", B, rows, cols, C);
-    if (interp != SVAE_ALIGN_BILINEAR && interp != SVAE_ALIGN_BICUBIC)
-        return fail(SVAE_E_INVALID, "svae_align_images: unknown interpolation %d", interp);
-    const long total = (long)B * rows * cols * C;
-    if (!y || !aligned || (y < aligned + total && aligned < y + total))
-        return fail(SVAE_E_INVALID, "svae_align_images: y and aligned must be two buffers that do not overlap");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Scope prof(K_AUGMENT, st);
-    const AlignGeo g{B, rows, cols, C};
-    if (interp == SVAE_ALIGN_BICUBIC)
-        hipLaunchKernelGGL(align_images_kernel<true>, dim3(blocks_for(total)), dim3(256), 0, st, y, theta, dx, aligned, cover, g);
-    else
-        hipLaunchKernelGGL(align_images_kernel<false>, dim3(blocks_for(total)), dim3(256), 0, st, y, theta, dx, aligned, cover, g);
-    return launch_status("svae_align_images");
-}
+}  // extern "C"
 
-int svae_class_sums_update(const float* aligned, const uint8_t* cover, const int32_t* label, int32_t B, int32_t N, int32_t C,
-                           int32_t n_classes, double* sum, double* count, svae_stream_t stream) {
-    if (B < 1 || N < 1 || C < 1 || C > SVAE_MAX_OUT || n_classes < 1 || n_classes > 4096 || (long)B * N * C > 0x7fffffffL ||
-        (long)n_classes * N * C > 0x7fffffffL)
-        return fail(SVAE_E_INVALID, "svae_class_sums_update: bad sizes B=%d N=%d C=%d n_classes=%d", B, N, C, n_classes);
-    if (!aligned || !label || !sum || !count) return fail(SVAE_E_INVALID, "svae_class_sums_update: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(class_sums_update_kernel, dim3(blocks_for((long)n_classes * N)), dim3(256), 0, st, aligned, cover, label, B, N,
-                       C, n_classes, sum, count);
-    return launch_status("svae_class_sums_update");
-}
+#include "analysis_api.h"  // the entry points of the analysis headers, and the rules they share
 
-namespace {
-const size_t CTF_LDS_MAX = 160 * 1024;
-const int CTF_SCRATCH_GROUPS = 512;  // workgroups of the scratch form (two per CU); each strides over the particles
-size_t ctf_lds_bytes(int n, int m) { return ((size_t)n * m * 3 + 2 * ((size_t)n + m)) * sizeof(double); }
-}  // namespace
-
-size_t svae_ctf_filter_workspace_bytes(int32_t count, int32_t n, int32_t m) {
-    if (count < 1 || n < 1 || m < 1) return 0;
-    if (ctf_lds_bytes(n, m) <= CTF_LDS_MAX) return 0;  // the whole transform fits the LDS of one CU
-    const size_t groups = (size_t)(count < CTF_SCRATCH_GROUPS ? count : CTF_SCRATCH_GROUPS);
-    return groups * (size_t)n * m * 3 * sizeof(double);
-}
-
-int svae_ctf_filter(const double* params, float* filters, int32_t count, int32_t n, int32_t m, double scale, void* ws,
-                    size_t ws_bytes, svae_stream_t stream) {
-    if (!params || !filters || count < 1 || n < 1 || m < 1) return fail(SVAE_E_INVALID, "svae_ctf_filter: bad arguments");
-    // the scratch form keeps only the 2 (n + m) twiddle factors in LDS: 16 (n + m) bytes must fit one CU's 160 KiB
-    const size_t tw = 2 * ((size_t)n + m) * sizeof(double);
-    if (tw > CTF_LDS_MAX)
-        return fail(SVAE_E_INVALID, "svae_ctf_filter: %d x %d filters are not supported (n + m must not exceed %zu)", n, m,
-                    CTF_LDS_MAX / (2 * sizeof(double)));
-    if (!(scale > 0.0)) return fail(SVAE_E_INVALID, "svae_ctf_filter: scale must be positive");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = ctf_lds_bytes(n, m);
-    Scope prof(K_AUGMENT, st);
-    if (lds <= CTF_LDS_MAX) {
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(ctf_filter_kernel<false>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return fail(SVAE_E_LAUNCH, "svae_ctf_filter: cannot reserve %zu bytes of LDS", lds);
-        hipLaunchKernelGGL(ctf_filter_kernel<false>, dim3(count), dim3(256), lds, st, params, filters, count, n, m, scale,
-                           static_cast<double*>(nullptr));
-    } else {
-        const size_t need = svae_ctf_filter_workspace_bytes(count, n, m);
-        if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
-            return fail(SVAE_E_WORKSPACE, "svae_ctf_filter: %d x %d filters need %zu bytes of 256-byte aligned scratch (got %zu)",
-                        n, m, need, ws_bytes);
-        const int groups = count < CTF_SCRATCH_GROUPS ? count : CTF_SCRATCH_GROUPS;
-        if (tw > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(ctf_filter_kernel<true>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)tw) != hipSuccess)
-            return fail(SVAE_E_LAUNCH, "svae_ctf_filter: cannot reserve %zu bytes of LDS", tw);
-        hipLaunchKernelGGL(ctf_filter_kernel<true>, dim3(groups), dim3(256), tw, st, params, filters, count, n, m, scale,
-                           static_cast<double*>(ws));
-    }
-    return launch_status("svae_ctf_filter");
-}
-
-// ---- CTF correction in Fourier space (include/svae_ctfcorr.h) ----
-namespace {
-size_t dft_lds_bytes(int n, int m) { return ((size_t)n * m * 4 + 2 * ((size_t)n + m)) * sizeof(double); }
-size_t dft_twiddle_bytes(int n, int m) { return 2 * ((size_t)n + m) * sizeof(double); }
-int dft_groups(int count) { return count < CTF_SCRATCH_GROUPS ? count : CTF_SCRATCH_GROUPS; }
-
-size_t dft_workspace_bytes(int count, int n, int m) {
-    if (count < 1 || n < 1 || m < 1) return 0;
-    if (dft_lds_bytes(n, m) <= CTF_LDS_MAX) return 0;  // both complex planes fit the LDS of one CU
-    return (size_t)dft_groups(count) * (size_t)n * m * 4 * sizeof(double);
-}
-
-// the plane-size and workspace rules svae_ctf_apply and svae_wiener_finish share; 0 or the refusal
-int dft_check(const char* who, int count, int n, int m, const void* ws, size_t ws_bytes) {
-    if (n < 2 || m < 2) return fail(SVAE_E_INVALID, "%s: planes must be at least 2 x 2 (got %d x %d)", who, n, m);
-    if (dft_twiddle_bytes(n, m) > CTF_LDS_MAX)
-        return fail(SVAE_E_INVALID, "%s: %d x %d planes are not supported (n + m must not exceed %zu)", who, n, m,
-                    CTF_LDS_MAX / (2 * sizeof(double)));
-    if ((long)count * n * m > 0x7fffffffL) return fail(SVAE_E_INVALID, "%s: %d planes of %d x %d are too many", who, count, n, m);
-    const size_t need = dft_workspace_bytes(count, n, m);
-    if (need && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255)))
-        return fail(SVAE_E_INVALID, "%s: %d x %d planes need a workspace of %zu bytes, 256-byte aligned (got %zu)", who, n, m, need,
-                    ws_bytes);
-    return SVAE_OK;
-}
-
-// launch one of the two plane kernels in its LDS or its workspace form
-extern "C++" template <class K, class... Args>
-int dft_launch(const char* who, K lds_kernel, K ws_kernel, int count, int n, int m, void* ws, hipStream_t st, Args... args) {
-    const size_t lds = dft_lds_bytes(n, m);
-    const bool scratch = lds > CTF_LDS_MAX;
-    const size_t bytes = scratch ? dft_twiddle_bytes(n, m) : lds;
-    K kernel = scratch ? ws_kernel : lds_kernel;
-    if (bytes > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)bytes) != hipSuccess)
-        return fail(SVAE_E_LAUNCH, "%s: cannot reserve %zu bytes of LDS", who, bytes);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(kernel, dim3(scratch ? dft_groups(count) : count), dim3(256), bytes, st, args...,
-                       static_cast<double*>(scratch ? ws : nullptr));
-    return launch_status(who);
-}
-}  // namespace
-
-size_t svae_ctf_apply_workspace_bytes(int32_t B, int32_t n, int32_t m) { return dft_workspace_bytes(B, n, m); }
-
-int svae_ctf_apply(const float* y, const double* params, int32_t B, int32_t n, int32_t m, double scale, int32_t mode, float* out,
-                   void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (B < 1) return fail(SVAE_E_INVALID, "svae_ctf_apply: B must be positive (got %d)", B);
-    if (mode != SVAE_CTF_FLIP && mode != SVAE_CTF_MULTIPLY) return fail(SVAE_E_INVALID, "svae_ctf_apply: unknown mode %d", mode);
-    if (!(scale > 0.0)) return fail(SVAE_E_INVALID, "svae_ctf_apply: scale must be positive");
-    if (const int rc = dft_check("svae_ctf_apply", B, n, m, ws, ws_bytes)) return rc;
-    const long total = (long)B * n * m;
-    if (!y || !out || !params) return fail(SVAE_E_INVALID, "svae_ctf_apply: null y, out or params");
-    if (y < out + total && out < y + total)
-        return fail(SVAE_E_INVALID, "svae_ctf_apply: y and out must be two buffers that do not overlap");
-    return dft_launch("svae_ctf_apply", ctf_apply_kernel<false>, ctf_apply_kernel<true>, B, n, m, ws,
-                      static_cast<hipStream_t>(stream), y, params, (int)B, (int)n, (int)m, scale, (int)mode, out);
-}
-
-int svae_ctf_power_update(const double* params, const int32_t* label, int32_t B, int32_t n, int32_t m, double scale,
-                          int32_t n_classes, double* den, svae_stream_t stream) {
-    if (B < 1 || n < 2 || m < 2 || n_classes < 1 || n_classes > 4096 || (long)n * m > 0x7fffffffL ||
-        (long)n_classes * n * m > 0x7fffffffL)
-        return fail(SVAE_E_INVALID, "svae_ctf_power_update: bad sizes B=%d n=%d m=%d n_classes=%d", B, n, m, n_classes);
-    if (!(scale > 0.0)) return fail(SVAE_E_INVALID, "svae_ctf_power_update: scale must be positive");
-    if (!params || !label || !den) return fail(SVAE_E_INVALID, "svae_ctf_power_update: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(ctf_power_update_kernel, dim3(blocks_for((long)n_classes * n * m)), dim3(256), 0, st, params, label, B, n, m,
-                       scale, n_classes, den);
-    return launch_status("svae_ctf_power_update");
-}
-
-size_t svae_wiener_finish_workspace_bytes(int32_t n_classes, int32_t n, int32_t m) { return dft_workspace_bytes(n_classes, n, m); }
-
-int svae_wiener_finish(const double* sum, const double* den, double lambda, int32_t n_classes, int32_t n, int32_t m, float* average,
-                       void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (n_classes < 1 || n_classes > 4096)
-        return fail(SVAE_E_INVALID, "svae_wiener_finish: n_classes %d outside 1..4096", n_classes);
-    if (!(lambda >= 0.0) || isinf(lambda)) return fail(SVAE_E_INVALID, "svae_wiener_finish: lambda must be finite and >= 0");
-    if (const int rc = dft_check("svae_wiener_finish", n_classes, n, m, ws, ws_bytes)) return rc;
-    if (!sum || !den || !average) return fail(SVAE_E_INVALID, "svae_wiener_finish: null sum, den or average");
-    return dft_launch("svae_wiener_finish", wiener_finish_kernel<false>, wiener_finish_kernel<true>, n_classes, n, m, ws,
-                      static_cast<hipStream_t>(stream), sum, den, lambda, (int)n_classes, (int)n, (int)m, average);
-}
-
-// ---- Fourier ring correlation (include/svae_frc.h) ----
-namespace {
-inline bool bytes_overlap(const void* p, size_t pn, const void* q, size_t qn) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + qn && b < a + pn;
-}
-// the size rules the two ring calls share, then ctfcorr's plane and workspace rules; 0 or the refusal
-int frc_check(const char* who, int planes, int n, int m, const void* ws, size_t ws_bytes) {
-    if (n < 2 || m < 2 || n > 1024 || m > 1024) return fail(SVAE_E_INVALID, "%s: n and m must be in 2..1024 (got %d x %d)", who, n, m);
-    if (planes < 1) return fail(SVAE_E_INVALID, "%s: planes must be positive (got %d)", who, planes);
-    return dft_check(who, planes, n, m, ws, ws_bytes);
-}
-}  // namespace
-
-size_t svae_frc_workspace_bytes(int32_t planes, int32_t n, int32_t m) { return dft_workspace_bytes(planes, n, m); }
-
-int svae_frc(const double* a, const double* b, int32_t planes, int32_t n, int32_t m, double mask_radius, double mask_edge,
-             double* sums, double* frc, int32_t* ring_count, void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (const int rc = frc_check("svae_frc", planes, n, m, ws, ws_bytes)) return rc;
-    if (!(mask_radius >= 0.0) || isinf(mask_radius)) return fail(SVAE_E_INVALID, "svae_frc: mask_radius must be finite and >= 0");
-    if (mask_radius > 0.0 && (!(mask_edge > 0.0) || isinf(mask_edge)))
-        return fail(SVAE_E_INVALID, "svae_frc: mask_edge must be finite and > 0 where mask_radius > 0");
-    if (!a || !b || !sums || !frc || !ring_count) return fail(SVAE_E_INVALID, "svae_frc: null a, b, sums, frc or ring_count");
-    const size_t R = (size_t)((n < m ? n : m) / 2 + 1);
-    const size_t in_bytes = (size_t)planes * n * m * sizeof(double);
-    const void* outs[3] = {sums, frc, ring_count};
-    const size_t out_bytes[3] = {(size_t)planes * R * 3 * sizeof(double), (size_t)planes * R * sizeof(double), R * sizeof(int32_t)};
-    for (int i = 0; i < 3; ++i)
-        if (bytes_overlap(a, in_bytes, outs[i], out_bytes[i]) || bytes_overlap(b, in_bytes, outs[i], out_bytes[i]))
-            return fail(SVAE_E_INVALID, "svae_frc: a and b must not overlap sums, frc or ring_count");
-    return dft_launch("svae_frc", frc_kernel<false>, frc_kernel<true>, planes, n, m, ws, static_cast<hipStream_t>(stream), a, b,
-                      (int)planes, (int)n, (int)m, mask_radius, mask_edge, sums, frc, reinterpret_cast<int*>(ring_count));
-}
-
-size_t svae_frc_filter_workspace_bytes(int32_t planes, int32_t n, int32_t m) { return dft_workspace_bytes(planes, n, m); }
-
-int svae_frc_filter(const double* x, const double* weight, int32_t planes, int32_t n, int32_t m, float* out, void* ws,
-                    size_t ws_bytes, svae_stream_t stream) {
-    if (const int rc = frc_check("svae_frc_filter", planes, n, m, ws, ws_bytes)) return rc;
-    if (!x || !weight || !out) return fail(SVAE_E_INVALID, "svae_frc_filter: null x, weight or out");
-    const size_t R = (size_t)((n < m ? n : m) / 2 + 1);
-    const size_t total = (size_t)planes * n * m;
-    if (bytes_overlap(x, total * sizeof(double), out, total * sizeof(float)) ||
-        bytes_overlap(weight, (size_t)planes * R * sizeof(double), out, total * sizeof(float)))
-        return fail(SVAE_E_INVALID, "svae_frc_filter: x and weight must not overlap out");
-    return dft_launch("svae_frc_filter", frc_filter_kernel<false>, frc_filter_kernel<true>, planes, n, m, ws,
-                      static_cast<hipStream_t>(stream), x, weight, (int)planes, (int)n, (int)m, out);
-}
-
-// ---- reference-based pose search (include/svae_refine.h) ----
-namespace {
-// doubles one workgroup keeps: the resampled plane and the image's score volume (+ 8 for the block sums in the LDS form)
-size_t refine_doubles(int rows, int cols, int C, int A, int S) {
-    return (size_t)rows * cols * C + (size_t)(2 * A + 1) * (2 * S + 1) * (2 * S + 1);
-}
-bool refine_sizes_ok(int B, int rows, int cols, int C, int A, int S) {
-    return B >= 1 && rows >= 2 && rows <= 1024 && cols >= 2 && cols <= 1024 && C >= 1 && C <= SVAE_MAX_OUT && A >= 0 && A <= 32 &&
-           S >= 0 && S <= 8;
-}
-bool refine_in_lds(int rows, int cols, int C, int A, int S) { return (refine_doubles(rows, cols, C, A, S) + 8) * sizeof(double) <= CTF_LDS_MAX; }
-// the slice of one workgroup in the workspace form, in doubles: a multiple of 256 bytes
-size_t refine_slice(int rows, int cols, int C, int A, int S) { return (refine_doubles(rows, cols, C, A, S) + 31) & ~size_t(31); }
-}  // namespace
-
-size_t svae_pose_search_workspace_bytes(int32_t B, int32_t rows, int32_t cols, int32_t C, int32_t A, int32_t S) {
-    if (!refine_sizes_ok(B, rows, cols, C, A, S) || refine_in_lds(rows, cols, C, A, S)) return 0;
-    return (size_t)dft_groups(B) * refine_slice(rows, cols, C, A, S) * sizeof(double);
-}
-
-int svae_pose_search(const float* y, const double* ref, const double* weight, const int32_t* ref_index, const float* pose_in,
-                     int32_t B, int32_t n_ref, int32_t rows, int32_t cols, int32_t C, int32_t A, double step, int32_t S,
-                     int32_t interp, float* pose_out, double* score, int32_t* offset, double* scores, void* ws, size_t ws_bytes,
-                     svae_stream_t stream) {
-    if (!refine_sizes_ok(B, rows, cols, C, A, S) || n_ref < 1)
-        return fail(SVAE_E_INVALID, "svae_pose_search: bad sizes B=%d n_ref=%d rows=%d cols=%d C=%d A=%d S=%d (rows, cols in 2..1024, "
-                    "C in 1..%d, A in 0..32, S in 0..8)", B, n_ref, rows, cols, C, A, S, SVAE_MAX_OUT);
-    if ((long)B * rows * cols * C > 0x7fffffffL || (long)n_ref * rows * cols * C > 0x7fffffffL)
-        return fail(SVAE_E_INVALID, "svae_pose_search: %d images or %d references of %d x %d x %d are too many", B, n_ref, rows, cols, C);
-    if (A > 0 && (!(step > 0.0) || isinf(step))) return fail(SVAE_E_INVALID, "svae_pose_search: step must be finite and > 0 where A > 0");
-    if (interp != SVAE_ALIGN_BILINEAR && interp != SVAE_ALIGN_BICUBIC)
-        return fail(SVAE_E_INVALID, "svae_pose_search: unknown interpolation %d", interp);
-    if (!y || !ref || !ref_index || !pose_in || !pose_out || !score || !offset)
-        return fail(SVAE_E_INVALID, "svae_pose_search: null y, ref, ref_index, pose_in, pose_out, score or offset");
-    const bool scratch = !refine_in_lds(rows, cols, C, A, S);
-    const size_t need = svae_pose_search_workspace_bytes(B, rows, cols, C, A, S);
-    if (scratch && (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255)))
-        return fail(SVAE_E_INVALID, "svae_pose_search: %d x %d x %d images with A=%d, S=%d need a workspace of %zu bytes, 256-byte "
-                    "aligned (got %zu)", rows, cols, C, A, S, need, ws_bytes);
-    using K = decltype(&pose_search_kernel<false, false>);
-    const bool cubic = interp == SVAE_ALIGN_BICUBIC;
-    K kernel = scratch ? (cubic ? pose_search_kernel<true, true> : pose_search_kernel<false, true>)
-                       : (cubic ? pose_search_kernel<true, false> : pose_search_kernel<false, false>);
-    const size_t lds = (scratch ? 8 : refine_doubles(rows, cols, C, A, S) + 8) * sizeof(double);
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-        return fail(SVAE_E_LAUNCH, "svae_pose_search: cannot reserve %zu bytes of LDS", lds);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const RefineGeo g{B, n_ref, rows, cols, C, A, S, A > 0 ? step : 0.0};
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(kernel, dim3(scratch ? dft_groups(B) : B), dim3(256), lds, st, y, ref, weight, reinterpret_cast<const int*>(ref_index),
-                       pose_in, g, pose_out, score, reinterpret_cast<int*>(offset), scores, static_cast<double*>(scratch ? ws : nullptr),
-                       (long)refine_slice(rows, cols, C, A, S));
-    return launch_status("svae_pose_search");
-}
-
-// ---- multi-reference alignment (include/svae_classify.h) ----
-namespace {
-size_t roundup32(size_t v) { return (v + 31) & ~size_t(31); }
-bool classify_sizes_ok(int B, int n_ref, int M, int rows, int cols, int C) {
-    return refine_sizes_ok(B, rows, cols, C, 0, 0) && n_ref >= 1 && M >= 1 && M <= 4096 && (long)B * rows * cols * C <= 0x7fffffffL &&
-           (long)n_ref * rows * cols * C <= 0x7fffffffL && (long)B * M <= 0x7fffffffL;
-}
-// doubles one workgroup keeps: the resampled plane and the M running maxima (+ 8 for the block sums in the LDS form)
-size_t classify_doubles(int M, int rows, int cols, int C) { return (size_t)rows * cols * C + (size_t)M; }
-bool classify_in_lds(int M, int rows, int cols, int C) { return (classify_doubles(M, rows, cols, C) + 8) * sizeof(double) <= CTF_LDS_MAX; }
-}  // namespace
-
-size_t svae_pose_classify_workspace_bytes(int32_t B, int32_t n_ref, int32_t M, int32_t rows, int32_t cols, int32_t C) {
-    if (!classify_sizes_ok(B, n_ref, M, rows, cols, C)) return 0;
-    size_t doubles = roundup32((size_t)n_ref);
-    if (!classify_in_lds(M, rows, cols, C)) doubles += (size_t)dft_groups(B) * roundup32(classify_doubles(M, rows, cols, C));
-    return doubles * sizeof(double);
-}
-
-int svae_pose_classify(const float* y, const double* ref, const double* weight, const int32_t* cand, const float* pose_in,
-                       int32_t B, int32_t n_ref, int32_t M, int32_t rows, int32_t cols, int32_t C, int32_t A, double step,
-                       int32_t S, int32_t interp, int32_t* choice, int32_t* ref_chosen, double* cand_score, double* margin,
-                       void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (!refine_sizes_ok(B, rows, cols, C, A, S) || n_ref < 1 || M < 1 || M > 4096)
-        return fail(SVAE_E_INVALID, "svae_pose_classify: bad sizes B=%d n_ref=%d M=%d rows=%d cols=%d C=%d A=%d S=%d (M in 1..4096, rows, "
-                    "cols in 2..1024, C in 1..%d, A in 0..32, S in 0..8)", B, n_ref, M, rows, cols, C, A, S, SVAE_MAX_OUT);
-    if (!classify_sizes_ok(B, n_ref, M, rows, cols, C))
-        return fail(SVAE_E_INVALID, "svae_pose_classify: %d images or %d references of %d x %d x %d, or %d x %d candidates, are too many",
-                    B, n_ref, rows, cols, C, B, M);
-    if (A > 0 && (!(step > 0.0) || isinf(step))) return fail(SVAE_E_INVALID, "svae_pose_classify: step must be finite and > 0 where A > 0");
-    if (interp != SVAE_ALIGN_BILINEAR && interp != SVAE_ALIGN_BICUBIC)
-        return fail(SVAE_E_INVALID, "svae_pose_classify: unknown interpolation %d", interp);
-    if (!y || !ref || !cand || !pose_in || !choice || !ref_chosen || !cand_score)
-        return fail(SVAE_E_INVALID, "svae_pose_classify: null y, ref, cand, pose_in, choice, ref_chosen or cand_score");
-    const bool scratch = !classify_in_lds(M, rows, cols, C);
-    const size_t need = svae_pose_classify_workspace_bytes(B, n_ref, M, rows, cols, C);
-    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
-        return fail(SVAE_E_INVALID, "svae_pose_classify: %d references and %d x %d x %d images with M=%d need a workspace of %zu bytes, "
-                    "256-byte aligned (got %zu)", n_ref, rows, cols, C, M, need, ws_bytes);
-    using K = decltype(&pose_classify_kernel<false, false>);
-    const bool cubic = interp == SVAE_ALIGN_BICUBIC;
-    K kernel = scratch ? (cubic ? pose_classify_kernel<true, true> : pose_classify_kernel<false, true>)
-                       : (cubic ? pose_classify_kernel<true, false> : pose_classify_kernel<false, false>);
-    const size_t lds = (scratch ? 8 : classify_doubles(M, rows, cols, C) + 8) * sizeof(double);
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-        return fail(SVAE_E_LAUNCH, "svae_pose_classify: cannot reserve %zu bytes of LDS", lds);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const ClassifyGeo g{B, n_ref, M, rows, cols, C, A, S, A > 0 ? step : 0.0};
-    double* norms = static_cast<double*>(ws);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(classify_norms_kernel, dim3(n_ref), dim3(256), 0, st, ref, weight, rows * cols * C, C, norms);
-    hipLaunchKernelGGL(kernel, dim3(scratch ? dft_groups(B) : B), dim3(256), lds, st, y, ref, weight, reinterpret_cast<const int*>(cand),
-                       pose_in, g, static_cast<const double*>(norms), reinterpret_cast<int*>(choice), reinterpret_cast<int*>(ref_chosen),
-                       cand_score, margin, scratch ? norms + roundup32((size_t)n_ref) : nullptr,
-                       (long)roundup32(classify_doubles(M, rows, cols, C)));
-    return launch_status("svae_pose_classify");
-}
-
-// ---- k-means over the content latents (include/svae_cluster.h) ----
-namespace {
-// the geometry and workspace rules the two k-means calls share; 0 or the refusal
-int kmeans_check(const char* who, int64_t N, int32_t D, int32_t k, const void* ws, size_t ws_bytes) {
-    if (D < 1 || D > kKmeansMaxD || k < 1 || k > kKmeansMaxK || N < k || N > 0x7fffffffLL)
-        return fail(SVAE_E_INVALID, "%s: bad sizes N=%lld D=%d k=%d (1 <= D <= %d, 1 <= k <= %d, k <= N < 2^31)", who, (long long)N, D, k,
-                    kKmeansMaxD, kKmeansMaxK);
-    if (!ws) return fail(SVAE_E_WORKSPACE, "%s: null workspace", who);
-    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(SVAE_E_WORKSPACE, "%s: workspace not 256-byte aligned", who);
-    const size_t need = kmeans_ws_words((long)N, D, k) * 8;
-    if (ws_bytes < need) return fail(SVAE_E_WORKSPACE, "%s: workspace too small: %zu < %zu", who, ws_bytes, need);
-    return SVAE_OK;
-}
-inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; }
-}  // namespace
-
-size_t svae_kmeans_workspace_bytes(int64_t N, int32_t D, int32_t k) {
-    if (D < 1 || D > kKmeansMaxD || k < 1 || k > kKmeansMaxK || N < k || N > 0x7fffffffLL) return 0;
-    return kmeans_ws_words((long)N, D, k) * 8;
-}
-
-int svae_kmeans_seed(const float* x, int64_t N, int32_t D, int32_t k, const double* u, double* centres, int32_t* seed_index,
-                     void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (!x || !u || !centres || !seed_index) return fail(SVAE_E_INVALID, "svae_kmeans_seed: null x, u, centres or seed_index");
-    if (misaligned8(u) || misaligned8(centres)) return fail(SVAE_E_INVALID, "svae_kmeans_seed: u and centres must be 8-byte aligned");
-    if (const int rc = kmeans_check("svae_kmeans_seed", N, D, k, ws, ws_bytes)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long P = kmeans_chunk((long)N);
-    const int chunks = (int)(((long)N + P - 1) / P);
-    const KmeansWs w = kmeans_ws(ws, (long)N, D, k);
-    Scope prof(K_AUGMENT, st);
-    for (int j = 0; j < k; ++j) {
-        if (j > 0) {
-            const int first = j == 1 ? 1 : 0;
-            if (D <= 4)
-                hipLaunchKernelGGL(kmeans_seed_dist_kernel<4>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, P, centres, j - 1, first, w);
-            else if (D <= 16)
-                hipLaunchKernelGGL(kmeans_seed_dist_kernel<16>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, P, centres, j - 1, first, w);
-            else
-                hipLaunchKernelGGL(kmeans_seed_dist_kernel<64>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, P, centres, j - 1, first, w);
-        }
-        hipLaunchKernelGGL(kmeans_seed_pick_kernel, dim3(1), dim3(256), 0, st, x, (long)N, D, P, chunks, j, u, centres, seed_index, w);
-    }
-    return launch_status("svae_kmeans_seed");
-}
-
-int svae_kmeans_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t update, double* centres, int32_t* label,
-                     int64_t* members, svae_kmeans_record* rec, void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (!x || !centres || !label || !members || !rec) return fail(SVAE_E_INVALID, "svae_kmeans_step: null x, centres, label, members or rec");
-    if (misaligned8(centres) || misaligned8(members) || misaligned8(rec))
-        return fail(SVAE_E_INVALID, "svae_kmeans_step: centres, members and rec must be 8-byte aligned");
-    if (const int rc = kmeans_check("svae_kmeans_step", N, D, k, ws, ws_bytes)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long P = kmeans_chunk((long)N);
-    const int chunks = (int)(((long)N + P - 1) / P);
-    const KmeansWs w = kmeans_ws(ws, (long)N, D, k);
-    const int up = update ? 1 : 0;
-    const long long* iterations = reinterpret_cast<const long long*>(&rec->iterations);
-    long long* mem = reinterpret_cast<long long*>(members);
-    Scope prof(K_AUGMENT, st);
-    if (D <= 4)
-        hipLaunchKernelGGL(kmeans_assign_kernel<4>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, centres, label, iterations, w);
-    else if (D <= 16)
-        hipLaunchKernelGGL(kmeans_assign_kernel<16>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, centres, label, iterations, w);
-    else
-        hipLaunchKernelGGL(kmeans_assign_kernel<64>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, centres, label, iterations, w);
-    hipLaunchKernelGGL(kmeans_accumulate_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, up, label, w);
-    hipLaunchKernelGGL(kmeans_tail_kernel, dim3(blocks_for(up ? (long)k * D : (long)k)), dim3(256), 0, st, D, k, chunks, up, centres, mem,
-                       rec, w);
-    return launch_status("svae_kmeans_step");
-}
-
-// ---- the Gaussian mixture over the content latents (include/svae_gmm.h) ----
-namespace {
-// the pointer, range, geometry and workspace rules the two mixture calls share; 0 or the refusal
-int gmm_check(const char* who, const void* x, int64_t N, int32_t D, int32_t k, const void* labels, double reg, double tol,
-              const void* weight, const void* mean, const void* var, const void* resp, const void* loglik_point, const void* rec,
-              const void* ws, size_t ws_bytes) {
-    if (!x || !labels || !weight || !mean || !var || !resp || !rec)
-        return fail(SVAE_E_INVALID, "%s: null x, labels, weight, mean, var, resp or rec", who);
-    if (misaligned8(weight) || misaligned8(mean) || misaligned8(var) || misaligned8(resp) || misaligned8(rec) || misaligned8(loglik_point))
-        return fail(SVAE_E_INVALID, "%s: weight, mean, var, resp, loglik_point and rec must be 8-byte aligned", who);
-    if (!(reg > 0.0) || !std::isfinite(reg)) return fail(SVAE_E_INVALID, "%s: reg = %g must be a finite number > 0", who, reg);
-    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SVAE_E_INVALID, "%s: tol = %g must be a finite number >= 0", who, tol);
-    if (D < 1 || D > kKmeansMaxD || k < 1 || k > kKmeansMaxK || N < k || N > 0x7fffffffLL)
-        return fail(SVAE_E_INVALID, "%s: bad sizes N=%lld D=%d k=%d (1 <= D <= %d, 1 <= k <= %d, k <= N < 2^31)", who, (long long)N, D, k,
-                    kKmeansMaxD, kKmeansMaxK);
-    if (!ws) return fail(SVAE_E_WORKSPACE, "%s: null workspace", who);
-    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(SVAE_E_WORKSPACE, "%s: workspace not 256-byte aligned", who);
-    const size_t need = gmm_ws_words((long)N, D, k) * 8;
-    if (ws_bytes < need) return fail(SVAE_E_WORKSPACE, "%s: workspace too small: %zu < %zu", who, ws_bytes, need);
-    return SVAE_OK;
-}
-}  // namespace
-
-size_t svae_gmm_workspace_bytes(int64_t N, int32_t D, int32_t k) {
-    if (D < 1 || D > kKmeansMaxD || k < 1 || k > kKmeansMaxK || N < k || N > 0x7fffffffLL) return 0;
-    return gmm_ws_words((long)N, D, k) * 8;
-}
-
-int svae_gmm_init(const float* x, int64_t N, int32_t D, int32_t k, const int32_t* label_in, double reg, double* weight, double* mean,
-                  double* var, double* resp, svae_gmm_record* rec, void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (const int rc = gmm_check("svae_gmm_init", x, N, D, k, label_in, reg, 0.0, weight, mean, var, resp, nullptr, rec, ws, ws_bytes)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long P = kmeans_chunk((long)N);
-    const int chunks = (int)(((long)N + P - 1) / P);
-    const GmmWs w = gmm_ws(ws, (long)N, D, k);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(gmm_onehot_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, reinterpret_cast<const int*>(label_in), resp, w);
-    hipLaunchKernelGGL(gmm_accumulate_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean),
-                       static_cast<const double*>(resp), static_cast<const long long*>(nullptr), w);
-    hipLaunchKernelGGL(gmm_tail_kernel, dim3(blocks_for((long)k * (D + 1))), dim3(256), 0, st, D, k, chunks, (int)kGmmInit, reg, 0.0, weight,
-                       mean, var, rec, w);
-    return launch_status("svae_gmm_init");
-}
-
-int svae_gmm_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t update, double reg, double tol, double* weight,
-                  double* mean, double* var, double* resp, int32_t* label, double* loglik_point, svae_gmm_record* rec, void* ws,
-                  size_t ws_bytes, svae_stream_t stream) {
-    if (const int rc = gmm_check("svae_gmm_step", x, N, D, k, label, reg, tol, weight, mean, var, resp, loglik_point, rec, ws, ws_bytes))
-        return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long P = kmeans_chunk((long)N);
-    const int chunks = (int)(((long)N + P - 1) / P);
-    const GmmWs w = gmm_ws(ws, (long)N, D, k);
-    int* lab = reinterpret_cast<int*>(label);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(gmm_prologue_kernel, dim3(blocks_for((long)k)), dim3(256), 0, st, D, k, static_cast<const double*>(weight),
-                       static_cast<const double*>(var), static_cast<const svae_gmm_record*>(rec), w);
-    if (D <= 4)
-        hipLaunchKernelGGL(gmm_e_kernel<4>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean), resp, lab,
-                           loglik_point, w);
-    else if (D <= 16)
-        hipLaunchKernelGGL(gmm_e_kernel<16>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean), resp, lab,
-                           loglik_point, w);
-    else
-        hipLaunchKernelGGL(gmm_e_kernel<64>, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean), resp, lab,
-                           loglik_point, w);
-    if (update)
-        hipLaunchKernelGGL(gmm_accumulate_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, k, P, static_cast<const double*>(mean),
-                           static_cast<const double*>(resp), static_cast<const long long*>(w.snap), w);
-    hipLaunchKernelGGL(gmm_tail_kernel, dim3(update ? blocks_for((long)k * (D + 1)) : 1), dim3(256), 0, st, D, k, chunks,
-                       update ? (int)kGmmStep : (int)kGmmLabelOnly, reg, tol, weight, mean, var, rec, w);
-    return launch_status("svae_gmm_step");
-}
-
-// ---- principal axes of the content latents (include/svae_pca.h) ----
-size_t svae_pca_workspace_bytes(int64_t N, int32_t D, int32_t G) {
-    if (!pca_sizes_ok(N, D, G)) return 0;
-    return pca_ws_words((long)N, D, G) * 8;
-}
-
-int svae_pca_moments(const float* x, int64_t N, int32_t D, int32_t G, const int32_t* group, int64_t* count, double* mean,
-                     double* cov, void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (!x || !count || !mean || !cov) return fail(SVAE_E_INVALID, "svae_pca_moments: null x, count, mean or cov");
-    if (misaligned8(count) || misaligned8(mean) || misaligned8(cov))
-        return fail(SVAE_E_INVALID, "svae_pca_moments: count, mean and cov must be 8-byte aligned");
-    if (!pca_sizes_ok(N, D, G))
-        return fail(SVAE_E_INVALID, "svae_pca_moments: bad sizes N=%lld D=%d G=%d (1 <= D <= %d, 1 <= G <= %d, G D (D + 1) / 2 <= %d, "
-                    "1 <= N < 2^31)", (long long)N, D, G, kKmeansMaxD, kPcaMaxG, kPcaMaxPartials);
-    if (!group && G != 1) return fail(SVAE_E_INVALID, "svae_pca_moments: a null group needs G == 1 (got %d)", G);
-    if (!ws) return fail(SVAE_E_WORKSPACE, "svae_pca_moments: null workspace");
-    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(SVAE_E_WORKSPACE, "svae_pca_moments: workspace not 256-byte aligned");
-    const size_t need = pca_ws_words((long)N, D, G) * 8;
-    if (ws_bytes < need) return fail(SVAE_E_WORKSPACE, "svae_pca_moments: workspace too small: %zu < %zu", ws_bytes, need);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long P = kmeans_chunk((long)N);
-    const int chunks = (int)(((long)N + P - 1) / P);
-    const PcaWs w = pca_ws(ws, (long)N, D, G);
-    long long* cnt = reinterpret_cast<long long*>(count);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(pca_sums_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, G, P, reinterpret_cast<const int*>(group), w);
-    hipLaunchKernelGGL(pca_mean_kernel, dim3(blocks_for((long)G * (D + 1))), dim3(256), 0, st, D, G, chunks, cnt, mean, w);
-    hipLaunchKernelGGL(pca_products_kernel, dim3(chunks), dim3(256), 0, st, x, (long)N, D, G, P, static_cast<const double*>(mean), w);
-    hipLaunchKernelGGL(pca_cov_kernel, dim3(blocks_for((long)G * (D * (D + 1) / 2))), dim3(256), 0, st, D, G, chunks,
-                       static_cast<const long long*>(cnt), cov, w);
-    return launch_status("svae_pca_moments");
-}
-
-int svae_pca_eigen(const double* cov, int32_t D, int32_t G, double* eigenvalues, double* components, int32_t* sweeps,
-                   double* off_norm, svae_stream_t stream) {
-    if (!cov || !eigenvalues || !components || !sweeps || !off_norm)
-        return fail(SVAE_E_INVALID, "svae_pca_eigen: null cov, eigenvalues, components, sweeps or off_norm");
-    if (misaligned8(cov) || misaligned8(eigenvalues) || misaligned8(components) || misaligned8(off_norm))
-        return fail(SVAE_E_INVALID, "svae_pca_eigen: cov, eigenvalues, components and off_norm must be 8-byte aligned");
-    if (!pca_sizes_ok(1, D, G))
-        return fail(SVAE_E_INVALID, "svae_pca_eigen: bad sizes D=%d G=%d (1 <= D <= %d, 1 <= G <= %d, G D (D + 1) / 2 <= %d)", D, G,
-                    kKmeansMaxD, kPcaMaxG, kPcaMaxPartials);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(pca_eigen_kernel, dim3(G), dim3(256), 0, st, cov, D, eigenvalues, components, reinterpret_cast<int*>(sweeps), off_norm);
-    return launch_status("svae_pca_eigen");
-}
-
-int svae_pca_project(const float* x, int64_t N, int32_t D, int32_t G, int32_t P, const int32_t* group, const int64_t* count,
-                     const double* mean, const double* components, double* proj, svae_stream_t stream) {
-    if (!x || !count || !mean || !components || !proj) return fail(SVAE_E_INVALID, "svae_pca_project: null x, count, mean, components or proj");
-    if (misaligned8(count) || misaligned8(mean) || misaligned8(components) || misaligned8(proj))
-        return fail(SVAE_E_INVALID, "svae_pca_project: count, mean, components and proj must be 8-byte aligned");
-    if (!pca_sizes_ok(N, D, G))
-        return fail(SVAE_E_INVALID, "svae_pca_project: bad sizes N=%lld D=%d G=%d (1 <= D <= %d, 1 <= G <= %d, G D (D + 1) / 2 <= %d, "
-                    "1 <= N < 2^31)", (long long)N, D, G, kKmeansMaxD, kPcaMaxG, kPcaMaxPartials);
-    if (P < 1 || P > D) return fail(SVAE_E_INVALID, "svae_pca_project: P = %d must be in 1..D = %d", P, D);
-    if (!group && G != 1) return fail(SVAE_E_INVALID, "svae_pca_project: a null group needs G == 1 (got %d)", G);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(pca_project_kernel, dim3(blocks_for((long)N * P)), dim3(256), 0, st, x, (long)N, D, G, P,
-                       reinterpret_cast<const int*>(group), reinterpret_cast<const long long*>(count), mean, components, proj);
-    return launch_status("svae_pca_project");
-}
-
-// ---- maximum-likelihood class averages (include/svae_expect.h) ----
-namespace {
-bool expect_sizes_ok(int B, int n_ref, int M, int rows, int cols, int C, int A, int S) {
-    return refine_sizes_ok(B, rows, cols, C, A, S) && n_ref >= 1 && M >= 1 && M <= kExpectMaxSlots &&
-           (long)B * rows * cols * C <= 0x7fffffffL && (long)n_ref * rows * cols * C <= 0x7fffffffL &&
-           (long)B * M * rows * cols * C <= 0x7fffffffL;
-}
-// doubles one workgroup keeps beside the fixed ones: the resampled plane, its coverage and the M log-weight volumes
-size_t expect_doubles(int M, int rows, int cols, int C, int A, int S) {
-    return (size_t)rows * cols * C + (size_t)rows * cols + (size_t)M * (2 * A + 1) * (2 * S + 1) * (2 * S + 1);
-}
-bool expect_in_lds(int M, int rows, int cols, int C, int A, int S) {
-    return (expect_doubles(M, rows, cols, C, A, S) + kExpectFixed) * sizeof(double) <= CTF_LDS_MAX;
-}
-}  // namespace
-
-size_t svae_pose_expect_workspace_bytes(int32_t B, int32_t n_ref, int32_t M, int32_t rows, int32_t cols, int32_t C, int32_t A,
-                                        int32_t S) {
-    if (!expect_sizes_ok(B, n_ref, M, rows, cols, C, A, S)) return 0;
-    size_t doubles = roundup32((size_t)n_ref);
-    if (!expect_in_lds(M, rows, cols, C, A, S)) doubles += (size_t)dft_groups(B) * roundup32(expect_doubles(M, rows, cols, C, A, S));
-    return doubles * sizeof(double);
-}
-
-int svae_pose_expect(const float* y, const double* ref, const double* weight, const double* log_prior, const int32_t* cand,
-                     const float* pose_in, int32_t B, int32_t n_ref, int32_t M, int32_t rows, int32_t cols, int32_t C, int32_t A,
-                     double step, int32_t S, int32_t interp, double inv_sigma2, double* contrib, double* cover_w,
-                     double* class_post, double* log_evidence, int32_t* best, void* ws, size_t ws_bytes, svae_stream_t stream) {
-    if (!refine_sizes_ok(B, rows, cols, C, A, S) || n_ref < 1 || M < 1 || M > kExpectMaxSlots)
-        return fail(SVAE_E_INVALID, "svae_pose_expect: bad sizes B=%d n_ref=%d M=%d rows=%d cols=%d C=%d A=%d S=%d (M in 1..%d, rows, "
-                    "cols in 2..1024, C in 1..%d, A in 0..32, S in 0..8)", B, n_ref, M, rows, cols, C, A, S, kExpectMaxSlots, SVAE_MAX_OUT);
-    if (!expect_sizes_ok(B, n_ref, M, rows, cols, C, A, S))
-        return fail(SVAE_E_INVALID, "svae_pose_expect: %d images or %d references of %d x %d x %d, or %d x %d contribution rows, are too "
-                    "many", B, n_ref, rows, cols, C, B, M);
-    if (A > 0 && (!(step > 0.0) || isinf(step))) return fail(SVAE_E_INVALID, "svae_pose_expect: step must be finite and > 0 where A > 0");
-    if (interp != SVAE_ALIGN_BILINEAR && interp != SVAE_ALIGN_BICUBIC)
-        return fail(SVAE_E_INVALID, "svae_pose_expect: unknown interpolation %d", interp);
-    if (!(inv_sigma2 >= 0.0) || !std::isfinite(inv_sigma2))
-        return fail(SVAE_E_INVALID, "svae_pose_expect: inv_sigma2 = %g must be a finite number >= 0", inv_sigma2);
-    if (!y || !ref || !cand || !pose_in || !contrib || !cover_w || !class_post || !log_evidence || !best)
-        return fail(SVAE_E_INVALID, "svae_pose_expect: null y, ref, cand, pose_in, contrib, cover_w, class_post, log_evidence or best");
-    const bool scratch = !expect_in_lds(M, rows, cols, C, A, S);
-    const size_t need = svae_pose_expect_workspace_bytes(B, n_ref, M, rows, cols, C, A, S);
-    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
-        return fail(SVAE_E_INVALID, "svae_pose_expect: %d references and %d x %d x %d images with M=%d, A=%d, S=%d need a workspace of "
-                    "%zu bytes, 256-byte aligned (got %zu)", n_ref, rows, cols, C, M, A, S, need, ws_bytes);
-    using K = decltype(&pose_expect_kernel<false, false>);
-    const bool cubic = interp == SVAE_ALIGN_BICUBIC;
-    K kernel = scratch ? (cubic ? pose_expect_kernel<true, true> : pose_expect_kernel<false, true>)
-                       : (cubic ? pose_expect_kernel<true, false> : pose_expect_kernel<false, false>);
-    const size_t lds = ((scratch ? 0 : expect_doubles(M, rows, cols, C, A, S)) + kExpectFixed) * sizeof(double);
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) != hipSuccess)
-        return fail(SVAE_E_LAUNCH, "svae_pose_expect: cannot reserve %zu bytes of LDS", lds);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const ExpectGeo g{B, n_ref, M, rows, cols, C, A, S, A > 0 ? step : 0.0, inv_sigma2};
-    double* hn = static_cast<double*>(ws);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(expect_norms_kernel, dim3(n_ref), dim3(256), 0, st, ref, weight, rows * cols * C, C, hn);
-    hipLaunchKernelGGL(kernel, dim3(scratch ? dft_groups(B) : B), dim3(256), lds, st, y, ref, weight, log_prior,
-                       reinterpret_cast<const int*>(cand), pose_in, g, static_cast<const double*>(hn), contrib, cover_w, class_post,
-                       log_evidence, reinterpret_cast<int*>(best), scratch ? hn + roundup32((size_t)n_ref) : nullptr,
-                       (long)roundup32(expect_doubles(M, rows, cols, C, A, S)));
-    return launch_status("svae_pose_expect");
-}
-
-int svae_expect_sums_update(const double* contrib, const double* cover_w, const int32_t* cand, const int32_t* target, int32_t B,
-                            int32_t M, int32_t N, int32_t C, int32_t n_ref, int32_t n_classes, double* sum, double* count,
-                            svae_stream_t stream) {
-    if (B < 1 || N < 1 || C < 1 || C > SVAE_MAX_OUT || n_classes < 1 || n_classes > 4096 || n_ref < 1 || M < 1 || M > kExpectMaxSlots ||
-        (long)B * N * C > 0x7fffffffL || (long)n_classes * N * C > 0x7fffffffL || (long)B * M * N * C > 0x7fffffffL)
-        return fail(SVAE_E_INVALID, "svae_expect_sums_update: bad sizes B=%d M=%d N=%d C=%d n_ref=%d n_classes=%d (M in 1..%d)", B, M, N, C,
-                    n_ref, n_classes, kExpectMaxSlots);
-    if (!contrib || !cover_w || !cand || !sum || !count) return fail(SVAE_E_INVALID, "svae_expect_sums_update: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Scope prof(K_AUGMENT, st);
-    hipLaunchKernelGGL(expect_sums_update_kernel, dim3(blocks_for((long)n_classes * N)), dim3(256), 0, st, contrib, cover_w,
-                       reinterpret_cast<const int*>(cand), reinterpret_cast<const int*>(target), B, M, N, C, n_ref, n_classes, sum, count);
-    return launch_status("svae_expect_sums_update");
-}
+extern "C" {
 
 int svae_gemm_mode_set(int mode) {
     if (mode != SVAE_GEMM_FP32 && mode != SVAE_GEMM_FP16X3) return fail(SVAE_E_INVALID, "svae_gemm_mode_set: unknown mode %d", mode);

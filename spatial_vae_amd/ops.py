@@ -36,6 +36,31 @@ def _buf(device, nbytes, key):
     return t
 
 
+def _workspace(entry, key, device, *geometry, required=False):
+    """(ws, ws_bytes) for the entry point `entry`: what its <entry>_workspace_bytes asks for that geometry, in the grow-only
+    buffer `key`.  Where it asks for nothing ws is None; with `required` there is a buffer all the same, and a `required` that is
+    a message is raised instead (0 then means a geometry the library refuses)."""
+    ws_bytes = getattr(_lib.lib(), entry + "_workspace_bytes")(*geometry)
+    if not ws_bytes and isinstance(required, str):
+        raise RuntimeError(required)
+    return (_buf(device, ws_bytes, key) if ws_bytes or required else None), ws_bytes
+
+
+def _hip_device(who, device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("spatial_vae_amd: %s must live on a HIP device (got %s); the MI355X path has no CPU "
+                           "fallback" % (who, device))
+    return device
+
+
+def _points(who, points, D):
+    _require_hip(points, "points")
+    if points.dtype != torch.float32 or points.dim() != 2 or points.size(1) != D or not points.is_contiguous():
+        raise RuntimeError("%s: points must be a contiguous (N, %d) float32 tensor, got %s %s"
+                           % (who, D, tuple(points.shape), points.dtype))
+
+
 def _f32(t):
     if t is None:
         return None
@@ -50,11 +75,7 @@ def _p(t):
 
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
-                 for name, (_, argtypes) in {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES,
-                                             **_lib.CTFCORR_SIGNATURES, **_lib.CLUSTER_SIGNATURES,
-                                             **_lib.FRC_SIGNATURES, **_lib.REFINE_SIGNATURES,
-                                             **_lib.CLASSIFY_SIGNATURES, **_lib.GMM_SIGNATURES,
-                                             **_lib.EXPECT_SIGNATURES, **_lib.PCA_SIGNATURES}.items()}
+                 for name, (_, argtypes) in _lib.ALL_SIGNATURES.items()}
 
 
 def _call(name, device, *args):
@@ -406,10 +427,7 @@ class IWStream:
     far.  Any number of chunks; the record it keeps on the device is a few doubles per image.  Forward only."""
 
     def __init__(self, B, inf_dim, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("spatial_vae_amd: IWStream must live on a HIP device (got %s); the MI355X path has no CPU "
-                               "fallback" % device)
+        device = _hip_device("IWStream", device)
         self.B, self.inf_dim, self.device = int(B), int(inf_dim), device
         nbytes = _lib.lib().svae_iw_stream_state_bytes(self.B, self.inf_dim)
         if nbytes == 0:
@@ -671,10 +689,7 @@ class ClassSums:
     accumulators, which are fractional from then on."""
 
     def __init__(self, n_classes, N, C, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("spatial_vae_amd: ClassSums must live on a HIP device (got %s); the MI355X path has no CPU "
-                               "fallback" % device)
+        device = _hip_device("ClassSums", device)
         self.n_classes, self.N, self.C, self.device = int(n_classes), int(N), int(C), device
         if self.n_classes < 1 or self.N < 1 or self.C < 1:
             raise RuntimeError("ClassSums: bad n_classes = %d, N = %d or C = %d" % (self.n_classes, self.N, self.C))
@@ -743,8 +758,7 @@ def ctf_apply(y, table, n, m, scale=1.0, mode="flip"):
     if tab.size(0) != B:
         raise RuntimeError("ctf_apply: %d rows of CTF parameters for %d images" % (tab.size(0), B))
     out = torch.empty_like(yc)
-    ws_bytes = _lib.lib().svae_ctf_apply_workspace_bytes(B, n, m)      # 0 while the planes fit the LDS (up to 71 x 71)
-    ws = _buf(y.device, ws_bytes, "ctfcorr") if ws_bytes else None
+    ws, ws_bytes = _workspace("svae_ctf_apply", "ctfcorr", y.device, B, n, m)    # none while the planes fit the LDS (up to 71 x 71)
     _call("svae_ctf_apply", y.device, yc, tab, B, n, m, float(scale), _lib.CTF_MODE[mode], out, ws, ws_bytes)
     return out.view_as(y)
 
@@ -756,10 +770,7 @@ class CtfPower:
     without atomics: the same sequence of updates gives the same bits."""
 
     def __init__(self, n_classes, n, m, device, scale=1.0):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("spatial_vae_amd: CtfPower must live on a HIP device (got %s); the MI355X path has no CPU "
-                               "fallback" % device)
+        device = _hip_device("CtfPower", device)
         self.n_classes, self.n, self.m, self.scale, self.device = int(n_classes), int(n), int(m), float(scale), device
         if self.n_classes < 1 or self.n < 2 or self.m < 2:
             raise RuntimeError("CtfPower: bad n_classes = %d, n = %d or m = %d" % (self.n_classes, self.n, self.m))
@@ -792,8 +803,7 @@ def wiener_finish(sum, den, lam, n, m):
         raise RuntimeError("wiener_finish: sum %s / den %s do not hold %d one-channel planes of %dx%d"
                            % (tuple(sum.shape), tuple(den.shape), n_classes, n, m))
     out = torch.empty(n_classes, n, m, dtype=torch.float32, device=sum.device)
-    ws_bytes = _lib.lib().svae_wiener_finish_workspace_bytes(n_classes, n, m)
-    ws = _buf(sum.device, ws_bytes, "ctfcorr") if ws_bytes else None
+    ws, ws_bytes = _workspace("svae_wiener_finish", "ctfcorr", sum.device, n_classes, n, m)
     _call("svae_wiener_finish", sum.device, sum.contiguous(), den.contiguous(), float(lam), n_classes, n, m, out, ws, ws_bytes)
     return out
 
@@ -813,8 +823,7 @@ def frc(a, b, n, m, mask_radius=0.0, mask_edge=0.0):
     sums = torch.empty(planes, R, 3, dtype=torch.float64, device=a.device)
     out = torch.empty(planes, R, dtype=torch.float64, device=a.device)
     ring_count = torch.empty(R, dtype=torch.int32, device=a.device)
-    ws_bytes = _lib.lib().svae_frc_workspace_bytes(planes, n, m)        # 0 while the planes fit the LDS (up to 71 x 71)
-    ws = _buf(a.device, ws_bytes, "frc") if ws_bytes else None
+    ws, ws_bytes = _workspace("svae_frc", "frc", a.device, planes, n, m)     # none while the planes fit the LDS (up to 71 x 71)
     _call("svae_frc", a.device, a.contiguous(), b.contiguous(), planes, n, m, float(mask_radius), float(mask_edge), sums, out,
           ring_count, ws, ws_bytes)
     return sums, out, ring_count
@@ -832,10 +841,36 @@ def frc_filter(x, weight, n, m):
         raise RuntimeError("frc_filter: x %s / weight %s do not hold %d planes of %dx%d and their %d rings"
                            % (tuple(x.shape), tuple(weight.shape), planes, n, m, R))
     out = torch.empty(planes, n, m, dtype=torch.float32, device=x.device)
-    ws_bytes = _lib.lib().svae_frc_filter_workspace_bytes(planes, n, m)
-    ws = _buf(x.device, ws_bytes, "frc") if ws_bytes else None
+    ws, ws_bytes = _workspace("svae_frc_filter", "frc", x.device, planes, n, m)
     _call("svae_frc_filter", x.device, x.contiguous(), weight.contiguous(), planes, n, m, out, ws, ws_bytes)
     return out
+
+
+def _pose_inputs(who, y, ref, weight, pose, rows, cols, interp, cand=None):
+    """The checks pose_search, pose_classify and pose_expect share on y, ref, weight, cand (where there is one), pose and interp.
+    Returns (y as contiguous fp32, B, N, C, n_ref, weight contiguous or None)."""
+    for name, t in (("y", y), ("ref", ref), ("cand", cand), ("pose", pose)):
+        if t is not None:
+            _require_hip(t, name)
+    if interp not in _lib.ALIGN_INTERP:
+        raise RuntimeError("%s: interp must be one of %s, got %r" % (who, sorted(_lib.ALIGN_INTERP), interp))
+    B, N = y.size(0), rows * cols
+    yc = _f32(y)
+    C = yc.numel() // (B * N) if B * N else 0
+    if C < 1 or C * B * N != yc.numel():
+        raise RuntimeError("%s: y %s does not hold %d images of %dx%d" % (who, tuple(y.shape), B, rows, cols))
+    if ref.dtype != torch.float64 or ref.numel() % (N * C) or not ref.numel():
+        raise RuntimeError("%s: ref %s (%s) must be float64 planes of %dx%dx%d" % (who, tuple(ref.shape), ref.dtype, rows, cols, C))
+    if weight is not None:
+        _require_hip(weight, "weight")
+        if weight.dtype != torch.float64 or weight.numel() != N:
+            raise RuntimeError("%s: weight must be %d float64 values, got %s (%s)" % (who, N, tuple(weight.shape), weight.dtype))
+        weight = weight.contiguous()
+    if cand is not None and (cand.dtype != torch.int32 or cand.dim() != 2 or cand.size(0) != B or cand.size(1) < 1):
+        raise RuntimeError("%s: cand must be (%d, M >= 1) int32, got %s (%s)" % (who, B, tuple(cand.shape), cand.dtype))
+    if pose.dtype != torch.float32 or tuple(pose.shape) != (B, 3):
+        raise RuntimeError("%s: pose must be (%d, 3) float32, got %s (%s)" % (who, B, tuple(pose.shape), pose.dtype))
+    return yc, B, N, C, ref.numel() // (N * C), weight
 
 
 PoseSearch = namedtuple("PoseSearch", "pose score offset scores")
@@ -849,35 +884,17 @@ def pose_search(y, ref, weight, ref_index, pose, rows, cols, angles, step, shift
     float64, weight (rows*cols) float64 or None, ref_index (B) int32, all on the device.  Returns PoseSearch(pose (B, 3) fp32,
     score (B) float64, offset (B, 4) int32 = k, sx, sy, flags, scores (B, 2 angles + 1, 2 shift + 1, 2 shift + 1) float64 or
     None) on the device; nothing is read back."""
-    for name, t in (("y", y), ("ref", ref), ("ref_index", ref_index), ("pose", pose)):
-        _require_hip(t, name)
-    if interp not in _lib.ALIGN_INTERP:
-        raise RuntimeError("pose_search: interp must be one of %s, got %r" % (sorted(_lib.ALIGN_INTERP), interp))
-    B, N = y.size(0), rows * cols
-    yc = _f32(y)
-    C = yc.numel() // (B * N) if B * N else 0
-    if C < 1 or C * B * N != yc.numel():
-        raise RuntimeError("pose_search: y %s does not hold %d images of %dx%d" % (tuple(y.shape), B, rows, cols))
-    if ref.dtype != torch.float64 or ref.numel() % (N * C) or not ref.numel():
-        raise RuntimeError("pose_search: ref %s (%s) must be float64 planes of %dx%dx%d" % (tuple(ref.shape), ref.dtype, rows, cols, C))
-    n_ref = ref.numel() // (N * C)
-    if weight is not None:
-        _require_hip(weight, "weight")
-        if weight.dtype != torch.float64 or weight.numel() != N:
-            raise RuntimeError("pose_search: weight must be %d float64 values, got %s (%s)" % (N, tuple(weight.shape), weight.dtype))
-        weight = weight.contiguous()
+    _require_hip(ref_index, "ref_index")
+    yc, B, N, C, n_ref, weight = _pose_inputs("pose_search", y, ref, weight, pose, rows, cols, interp)
     if ref_index.dtype != torch.int32 or ref_index.numel() != B:
         raise RuntimeError("pose_search: ref_index must be (%d) int32" % B)
-    if pose.dtype != torch.float32 or tuple(pose.shape) != (B, 3):
-        raise RuntimeError("pose_search: pose must be (%d, 3) float32, got %s (%s)" % (B, tuple(pose.shape), pose.dtype))
     A, S = int(angles), int(shift)
     dev = y.device
     out = torch.empty(B, 3, dtype=torch.float32, device=dev)
     score = torch.empty(B, dtype=torch.float64, device=dev)
     offset = torch.empty(B, 4, dtype=torch.int32, device=dev)
     scores = torch.empty(B, 2 * A + 1, 2 * S + 1, 2 * S + 1, dtype=torch.float64, device=dev) if return_scores and A >= 0 and S >= 0 else None
-    ws_bytes = _lib.lib().svae_pose_search_workspace_bytes(B, rows, cols, C, A, S)     # 0 while plane and volume fit the LDS
-    ws = _buf(dev, ws_bytes, "refine") if ws_bytes else None
+    ws, ws_bytes = _workspace("svae_pose_search", "refine", dev, B, rows, cols, C, A, S)     # none while plane and volume fit the LDS
     _call("svae_pose_search", dev, yc, ref.contiguous(), weight, ref_index.contiguous(), pose.contiguous(), B, n_ref, rows, cols, C,
           A, float(step), S, _lib.ALIGN_INTERP[interp], out, score, offset, scores, ws, ws_bytes)
     return PoseSearch(out, score, offset, scores)
@@ -894,35 +911,15 @@ def pose_classify(y, ref, weight, cand, pose, rows, cols, angles, step, shift, i
     (-1: none), ref_chosen its reference, margin the winner's lead over the best other live slot (+inf with fewer than two).
     Returns PoseClassify(choice (B) int32, ref_chosen (B) int32, cand_score (B, M) float64, margin (B) float64 or None) on the
     device; the pose is not refined (pose_search with ref_index = ref_chosen does that) and nothing is read back."""
-    for name, t in (("y", y), ("ref", ref), ("cand", cand), ("pose", pose)):
-        _require_hip(t, name)
-    if interp not in _lib.ALIGN_INTERP:
-        raise RuntimeError("pose_classify: interp must be one of %s, got %r" % (sorted(_lib.ALIGN_INTERP), interp))
-    B, N = y.size(0), rows * cols
-    yc = _f32(y)
-    C = yc.numel() // (B * N) if B * N else 0
-    if C < 1 or C * B * N != yc.numel():
-        raise RuntimeError("pose_classify: y %s does not hold %d images of %dx%d" % (tuple(y.shape), B, rows, cols))
-    if ref.dtype != torch.float64 or ref.numel() % (N * C) or not ref.numel():
-        raise RuntimeError("pose_classify: ref %s (%s) must be float64 planes of %dx%dx%d" % (tuple(ref.shape), ref.dtype, rows, cols, C))
-    n_ref = ref.numel() // (N * C)
-    if weight is not None:
-        _require_hip(weight, "weight")
-        if weight.dtype != torch.float64 or weight.numel() != N:
-            raise RuntimeError("pose_classify: weight must be %d float64 values, got %s (%s)" % (N, tuple(weight.shape), weight.dtype))
-        weight = weight.contiguous()
-    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.size(0) != B or cand.size(1) < 1:
-        raise RuntimeError("pose_classify: cand must be (%d, M >= 1) int32, got %s (%s)" % (B, tuple(cand.shape), cand.dtype))
-    if pose.dtype != torch.float32 or tuple(pose.shape) != (B, 3):
-        raise RuntimeError("pose_classify: pose must be (%d, 3) float32, got %s (%s)" % (B, tuple(pose.shape), pose.dtype))
+    yc, B, N, C, n_ref, weight = _pose_inputs("pose_classify", y, ref, weight, pose, rows, cols, interp, cand)
     A, S, M = int(angles), int(shift), cand.size(1)
     dev = y.device
     choice = torch.empty(B, dtype=torch.int32, device=dev)
     ref_chosen = torch.empty(B, dtype=torch.int32, device=dev)
     cand_score = torch.empty(B, M, dtype=torch.float64, device=dev)
     margin = torch.empty(B, dtype=torch.float64, device=dev) if return_margin else None
-    ws_bytes = _lib.lib().svae_pose_classify_workspace_bytes(B, n_ref, M, rows, cols, C)   # the norms, + plane slices above the LDS limit
-    ws = _buf(dev, ws_bytes, "classify")
+    # the norms, + plane slices above the LDS limit
+    ws, ws_bytes = _workspace("svae_pose_classify", "classify", dev, B, n_ref, M, rows, cols, C, required=True)
     _call("svae_pose_classify", dev, yc, ref.contiguous(), weight, cand.contiguous(), pose.contiguous(), B, n_ref, M, rows, cols, C,
           A, float(step), S, _lib.ALIGN_INTERP[interp], choice, ref_chosen, cand_score, margin, ws, ws_bytes)
     return PoseClassify(choice, ref_chosen, cand_score, margin)
@@ -939,29 +936,13 @@ def pose_expect(y, ref, weight, log_prior, cand, pose, rows, cols, angles, step,
     per slot; cover_w (B, M, rows*cols) float64: the same sum of their coverage; class_post (B, M) float64: the posterior of each
     slot; log_evidence (B) float64; best (B, 4) int32 = slot, k, sx, sy of the largest log-weight, slot -1 for a skipped image)
     on the device; nothing is read back."""
-    for name, t in (("y", y), ("ref", ref), ("cand", cand), ("pose", pose)):
-        _require_hip(t, name)
-    if interp not in _lib.ALIGN_INTERP:
-        raise RuntimeError("pose_expect: interp must be one of %s, got %r" % (sorted(_lib.ALIGN_INTERP), interp))
-    B, N = y.size(0), rows * cols
-    yc = _f32(y)
-    C = yc.numel() // (B * N) if B * N else 0
-    if C < 1 or C * B * N != yc.numel():
-        raise RuntimeError("pose_expect: y %s does not hold %d images of %dx%d" % (tuple(y.shape), B, rows, cols))
-    if ref.dtype != torch.float64 or ref.numel() % (N * C) or not ref.numel():
-        raise RuntimeError("pose_expect: ref %s (%s) must be float64 planes of %dx%dx%d" % (tuple(ref.shape), ref.dtype, rows, cols, C))
-    n_ref = ref.numel() // (N * C)
-    for name, t, n in (("weight", weight, N), ("log_prior", log_prior, n_ref)):
-        if t is not None:
-            _require_hip(t, name)
-            if t.dtype != torch.float64 or t.numel() != n:
-                raise RuntimeError("pose_expect: %s must be %d float64 values, got %s (%s)" % (name, n, tuple(t.shape), t.dtype))
-    weight = None if weight is None else weight.contiguous()
-    log_prior = None if log_prior is None else log_prior.contiguous()
-    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.size(0) != B or cand.size(1) < 1:
-        raise RuntimeError("pose_expect: cand must be (%d, M >= 1) int32, got %s (%s)" % (B, tuple(cand.shape), cand.dtype))
-    if pose.dtype != torch.float32 or tuple(pose.shape) != (B, 3):
-        raise RuntimeError("pose_expect: pose must be (%d, 3) float32, got %s (%s)" % (B, tuple(pose.shape), pose.dtype))
+    yc, B, N, C, n_ref, weight = _pose_inputs("pose_expect", y, ref, weight, pose, rows, cols, interp, cand)
+    if log_prior is not None:
+        _require_hip(log_prior, "log_prior")
+        if log_prior.dtype != torch.float64 or log_prior.numel() != n_ref:
+            raise RuntimeError("pose_expect: log_prior must be %d float64 values, got %s (%s)"
+                               % (n_ref, tuple(log_prior.shape), log_prior.dtype))
+        log_prior = log_prior.contiguous()
     A, S, M = int(angles), int(shift), cand.size(1)
     dev = y.device
     contrib = torch.empty(B, M, N, C, dtype=torch.float64, device=dev)
@@ -969,8 +950,8 @@ def pose_expect(y, ref, weight, log_prior, cand, pose, rows, cols, angles, step,
     class_post = torch.empty(B, M, dtype=torch.float64, device=dev)
     log_evidence = torch.empty(B, dtype=torch.float64, device=dev)
     best = torch.empty(B, 4, dtype=torch.int32, device=dev)
-    ws_bytes = _lib.lib().svae_pose_expect_workspace_bytes(B, n_ref, M, rows, cols, C, A, S)   # h, + slices above the LDS limit
-    ws = _buf(dev, ws_bytes, "expect")
+    # h, + slices above the LDS limit
+    ws, ws_bytes = _workspace("svae_pose_expect", "expect", dev, B, n_ref, M, rows, cols, C, A, S, required=True)
     _call("svae_pose_expect", dev, yc, ref.contiguous(), weight, log_prior, cand.contiguous(), pose.contiguous(), B, n_ref, M, rows,
           cols, C, A, float(step), S, _lib.ALIGN_INTERP[interp], float(inv_sigma2), contrib, cover_w, class_post, log_evidence, best,
           ws, ws_bytes)
@@ -988,10 +969,7 @@ class KMeans:
     RECORD_WORDS = ctypes.sizeof(_lib.KMeansRecord) // 8
 
     def __init__(self, k, D, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("spatial_vae_amd: KMeans must live on a HIP device (got %s); the MI355X path has no CPU "
-                               "fallback" % device)
+        device = _hip_device("KMeans", device)
         self.k, self.D, self.device = int(k), int(D), device
         if not (1 <= self.k <= 1024 and 1 <= self.D <= 64):
             raise RuntimeError("KMeans: k = %d must be in 1..1024 and D = %d in 1..64" % (self.k, self.D))
@@ -1001,10 +979,7 @@ class KMeans:
         contiguous on the device, N >= k; uniforms: k numbers in [0, 1), a host array or a float64 device tensor.  Returns
         KMeansFit of device tensors: label (N) int32, centres (k, D) float64, members (k) int64, record (the svae_kmeans_record
         as 6 int64 words, see read_record; its last word holds the inertia's bits) and seed_index (k) int32."""
-        _require_hip(points, "points")
-        if points.dtype != torch.float32 or points.dim() != 2 or points.size(1) != self.D or not points.is_contiguous():
-            raise RuntimeError("KMeans.fit: points must be a contiguous (N, %d) float32 tensor, got %s %s"
-                               % (self.D, tuple(points.shape), points.dtype))
+        _points("KMeans.fit", points, self.D)
         N, iters = points.size(0), int(iters)
         if N < self.k or iters < 0:
             raise RuntimeError("KMeans.fit: %d points for k = %d, iters = %d" % (N, self.k, iters))
@@ -1013,10 +988,8 @@ class KMeans:
             raise RuntimeError("KMeans.fit: uniforms must be %d float64 numbers, got %s %s" % (self.k, tuple(u.shape), u.dtype))
         u = u.reshape(-1).to(self.device).contiguous()
         dev, k, D = self.device, self.k, self.D
-        ws_bytes = _lib.lib().svae_kmeans_workspace_bytes(N, D, k)
-        if ws_bytes == 0:
-            raise RuntimeError("KMeans.fit: bad geometry N = %d, D = %d, k = %d" % (N, D, k))
-        ws = _buf(dev, ws_bytes, "kmeans")
+        ws, _ = _workspace("svae_kmeans", "kmeans", dev, N, D, k,
+                           required="KMeans.fit: bad geometry N = %d, D = %d, k = %d" % (N, D, k))
         out = KMeansFit(torch.empty(N, dtype=torch.int32, device=dev), torch.empty(k, D, dtype=torch.float64, device=dev),
                         torch.empty(k, dtype=torch.int64, device=dev), torch.zeros(self.RECORD_WORDS, dtype=torch.int64, device=dev),
                         torch.empty(k, dtype=torch.int32, device=dev))
@@ -1051,10 +1024,7 @@ class GaussianMixture:
     RECORD_WORDS = ctypes.sizeof(_lib.GmmRecord) // 8
 
     def __init__(self, k, D, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("spatial_vae_amd: GaussianMixture must live on a HIP device (got %s); the MI355X path has no CPU "
-                               "fallback" % device)
+        device = _hip_device("GaussianMixture", device)
         self.k, self.D, self.device = int(k), int(D), device
         if not (1 <= self.k <= 1024 and 1 <= self.D <= 64):
             raise RuntimeError("GaussianMixture: k = %d must be in 1..1024 and D = %d in 1..64" % (self.k, self.D))
@@ -1065,10 +1035,7 @@ class GaussianMixture:
         points: (N, D) fp32 contiguous on the device, N >= k.  Returns GmmFit of device tensors: weight (k), mean (k, D),
         var (k, D) and resp (N, k) float64, label (N) int32, loglik_point (N) float64, record (the svae_gmm_record as 6 int64
         words, see read_record) and trace (iters + 1) float64.  The inputs are left as they were."""
-        _require_hip(points, "points")
-        if points.dtype != torch.float32 or points.dim() != 2 or points.size(1) != self.D or not points.is_contiguous():
-            raise RuntimeError("GaussianMixture.fit: points must be a contiguous (N, %d) float32 tensor, got %s %s"
-                               % (self.D, tuple(points.shape), points.dtype))
+        _points("GaussianMixture.fit", points, self.D)
         N, iters, reg, tol = points.size(0), int(iters), float(reg), float(tol)
         dev, k, D = self.device, self.k, self.D
         if N < k or iters < 0:
@@ -1079,10 +1046,8 @@ class GaussianMixture:
             raise RuntimeError("GaussianMixture.fit: label must be %d int32 numbers on the device" % N)
         if not torch.is_tensor(centres) or centres.dtype != torch.float64 or tuple(centres.shape) != (k, D) or not centres.is_cuda:
             raise RuntimeError("GaussianMixture.fit: centres must be a (%d, %d) float64 tensor on the device" % (k, D))
-        ws_bytes = _lib.lib().svae_gmm_workspace_bytes(N, D, k)
-        if ws_bytes == 0:
-            raise RuntimeError("GaussianMixture.fit: bad geometry N = %d, D = %d, k = %d" % (N, D, k))
-        ws = _buf(dev, ws_bytes, "gmm")
+        ws, _ = _workspace("svae_gmm", "gmm", dev, N, D, k,
+                           required="GaussianMixture.fit: bad geometry N = %d, D = %d, k = %d" % (N, D, k))
         f64 = dict(dtype=torch.float64, device=dev)
         out = GmmFit(torch.empty(k, **f64), centres.contiguous().clone(), torch.empty(k, D, **f64), torch.empty(N, k, **f64),
                      torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, **f64),
@@ -1123,10 +1088,7 @@ class LatentPCA:
     MAX_PARTIALS = 32768        # G * D (D + 1) / 2
 
     def __init__(self, D, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("spatial_vae_amd: LatentPCA must live on a HIP device (got %s); the MI355X path has no CPU "
-                               "fallback" % device)
+        device = _hip_device("LatentPCA", device)
         self.D, self.device = int(D), device
         if not 1 <= self.D <= 64:
             raise RuntimeError("LatentPCA: D = %d must be in 1..64" % self.D)
@@ -1141,10 +1103,7 @@ class LatentPCA:
         on the device; group: (N) int32 on the device with entries in [0, G) (any other entry: in no group), or None with G == 1;
         P: the columns of proj, 1..D (default D).  Returns PcaFit of device tensors: count (G) int64, mean (G, D), cov (G, D, D),
         eigenvalues (G, D) descending, components (G, D, D) with rows as axes, sweeps (G) int32, off_norm (G) and proj (N, P)."""
-        _require_hip(points, "points")
-        if points.dtype != torch.float32 or points.dim() != 2 or points.size(1) != self.D or not points.is_contiguous():
-            raise RuntimeError("LatentPCA.fit: points must be a contiguous (N, %d) float32 tensor, got %s %s"
-                               % (self.D, tuple(points.shape), points.dtype))
+        _points("LatentPCA.fit", points, self.D)
         N, D, G, dev = points.size(0), self.D, int(G), self.device
         P = D if P is None else int(P)
         if not 1 <= P <= D:
@@ -1154,10 +1113,8 @@ class LatentPCA:
                 raise RuntimeError("LatentPCA.fit: without a group tensor G must be 1 (got %d)" % G)
         elif not torch.is_tensor(group) or group.dtype != torch.int32 or tuple(group.shape) != (N,) or not group.is_cuda:
             raise RuntimeError("LatentPCA.fit: group must be %d int32 numbers on the device" % N)
-        ws_bytes = _lib.lib().svae_pca_workspace_bytes(N, D, G)
-        if ws_bytes == 0:
-            raise RuntimeError("LatentPCA.fit: bad geometry N = %d, D = %d, G = %d (G D (D + 1) / 2 <= %d)" % (N, D, G, self.MAX_PARTIALS))
-        ws = _buf(dev, ws_bytes, "pca")
+        ws, _ = _workspace("svae_pca", "pca", dev, N, D, G, required="LatentPCA.fit: bad geometry N = %d, D = %d, G = %d (G D (D + 1) / 2 "
+                           "<= %d)" % (N, D, G, self.MAX_PARTIALS))
         group = None if group is None else group.contiguous()
         f64 = dict(dtype=torch.float64, device=dev)
         out = PcaFit(torch.empty(G, dtype=torch.int64, device=dev), torch.empty(G, D, **f64), torch.empty(G, D, D, **f64),

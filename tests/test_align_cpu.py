@@ -25,8 +25,8 @@ def _infer():
 # ---------------------------------------------------------------- the header and its table
 def test_align_binding_matches_its_header():
     """include/svae_align.h against _lib.ALIGN_SIGNATURES, both ways and type by type, with the parser and the type rules
-    tests/test_binding_cpu.py uses for svae.h; the header's two constants are _lib.ALIGN_INTERP; it adds no struct; the three
-    tables are pairwise disjoint; none of this adds an upper-case integer to the binding (those are svae.h's constants)."""
+    tests/test_binding_cpu.py uses for svae.h; the header's two constants are _lib.ALIGN_INTERP; it adds no struct; its table
+    is disjoint from all others; none of this adds an upper-case integer to the binding (those are svae.h's constants)."""
     from spatial_vae_amd import _lib
     path = os.path.join(ROOT, "include", "svae_align.h")
     with open(path) as f:
@@ -35,8 +35,9 @@ def test_align_binding_matches_its_header():
     assert H["structs"] == {} and len(H["functions"]) == 2
     assert H["constants"] == {"SVAE_ALIGN_" + k.upper(): v for k, v in _lib.ALIGN_INTERP.items()} == {"SVAE_ALIGN_BILINEAR": 0, "SVAE_ALIGN_BICUBIC": 1}
     assert set(H["functions"]) == set(_lib.ALIGN_SIGNATURES) == set(_lib.declared_in_header(path))
-    tables = [set(_lib.SIGNATURES), set(_lib.STREAM_SIGNATURES), set(_lib.ALIGN_SIGNATURES)]
-    assert not tables[0] & tables[1] and not tables[0] & tables[2] and not tables[1] & tables[2]
+    others = [t for h, t in _lib.HEADERS.items() if h != "svae_align.h"]
+    assert _lib.HEADERS["svae_align.h"] is _lib.ALIGN_SIGNATURES and len(others) == len(_lib.HEADERS) - 1
+    assert all(not set(t) & set(_lib.ALIGN_SIGNATURES) for t in others)
     for name, ((rbase, rptr), args) in H["functions"].items():
         restype, argtypes = _lib.ALIGN_SIGNATURES[name]
         assert restype in _allowed(rbase, rptr, _lib), name

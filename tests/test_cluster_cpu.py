@@ -24,8 +24,8 @@ def _infer():
 def test_cluster_binding_matches_its_header():
     """include/svae_cluster.h against _lib.CLUSTER_SIGNATURES, both ways and type by type, with the parser and the type rules
     tests/test_binding_cpu.py uses for svae.h (`rec` is the address of a record in device memory: c_void_p); the header adds no
-    constant and one struct, whose mirror _lib.KMeansRecord has its fields, size and offsets; the five tables are pairwise
-    disjoint; the loaded library has every entry with the table's types, and ops._POINTER_ARGS knows the device pointers."""
+    constant and one struct, whose mirror _lib.KMeansRecord has its fields, size and offsets; its table is disjoint from all
+    others; the loaded library has every entry with the table's types, and ops._POINTER_ARGS knows the device pointers."""
     from spatial_vae_amd import _lib
     path = os.path.join(ROOT, "include", "svae_cluster.h")
     with open(path) as f:
@@ -33,9 +33,9 @@ def test_cluster_binding_matches_its_header():
     H = parse_header(text.replace('#include "svae.h"', ""))
     assert H["constants"] == {} and list(H["structs"]) == ["svae_kmeans_record"] and len(H["functions"]) == 3
     assert set(H["functions"]) == set(_lib.CLUSTER_SIGNATURES) == set(_lib.declared_in_header(path))
-    tables = [set(_lib.SIGNATURES), set(_lib.STREAM_SIGNATURES), set(_lib.ALIGN_SIGNATURES), set(_lib.CTFCORR_SIGNATURES),
-              set(_lib.CLUSTER_SIGNATURES)]
-    assert all(not tables[i] & tables[j] for i in range(5) for j in range(i))
+    others = [t for h, t in _lib.HEADERS.items() if h != "svae_cluster.h"]
+    assert _lib.HEADERS["svae_cluster.h"] is _lib.CLUSTER_SIGNATURES and len(others) == len(_lib.HEADERS) - 1
+    assert all(not set(t) & set(_lib.CLUSTER_SIGNATURES) for t in others)
     for name, ((rbase, rptr), args) in H["functions"].items():
         restype, argtypes = _lib.CLUSTER_SIGNATURES[name]
         assert restype in _allowed(rbase, rptr, _lib), name

@@ -31,9 +31,9 @@ def _norm(a):
 # ---------------------------------------------------------------- the header and its table
 def test_ctfcorr_binding_matches_its_header():
     """include/svae_ctfcorr.h against _lib.CTFCORR_SIGNATURES, both ways and type by type, with the parser and the type rules
-    tests/test_binding_cpu.py uses for svae.h; the header's two constants are _lib.CTF_MODE; it adds no struct; the four tables
-    are pairwise disjoint; none of this adds an upper-case integer to the binding; the loaded library has every entry with the
-    table's types, and ops._POINTER_ARGS knows which arguments are device pointers."""
+    tests/test_binding_cpu.py uses for svae.h; the header's two constants are _lib.CTF_MODE; it adds no struct; its table is
+    disjoint from all others; none of this adds an upper-case integer to the binding; the loaded library has every entry with
+    the table's types, and ops._POINTER_ARGS knows which arguments are device pointers."""
     from spatial_vae_amd import _lib
     path = os.path.join(ROOT, "include", "svae_ctfcorr.h")
     with open(path) as f:
@@ -42,8 +42,9 @@ def test_ctfcorr_binding_matches_its_header():
     assert H["structs"] == {} and len(H["functions"]) == 5
     assert H["constants"] == {"SVAE_CTF_" + k.upper(): v for k, v in _lib.CTF_MODE.items()} == {"SVAE_CTF_FLIP": 0, "SVAE_CTF_MULTIPLY": 1}
     assert set(H["functions"]) == set(_lib.CTFCORR_SIGNATURES) == set(_lib.declared_in_header(path))
-    tables = [set(_lib.SIGNATURES), set(_lib.STREAM_SIGNATURES), set(_lib.ALIGN_SIGNATURES), set(_lib.CTFCORR_SIGNATURES)]
-    assert all(not tables[i] & tables[j] for i in range(4) for j in range(i))
+    others = [t for h, t in _lib.HEADERS.items() if h != "svae_ctfcorr.h"]
+    assert _lib.HEADERS["svae_ctfcorr.h"] is _lib.CTFCORR_SIGNATURES and len(others) == len(_lib.HEADERS) - 1
+    assert all(not set(t) & set(_lib.CTFCORR_SIGNATURES) for t in others)
     for name, ((rbase, rptr), args) in H["functions"].items():
         restype, argtypes = _lib.CTFCORR_SIGNATURES[name]
         assert restype in _allowed(rbase, rptr, _lib), name

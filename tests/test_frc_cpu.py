@@ -20,7 +20,7 @@ def _infer():
 # ---------------------------------------------------------------- the header and its table
 def test_frc_binding_matches_its_header():
     """include/svae_frc.h against _lib.FRC_SIGNATURES, both ways and type by type, with the parser and the type rules
-    tests/test_binding_cpu.py uses for svae.h; the header adds no constant and no struct; the six tables are pairwise disjoint;
+    tests/test_binding_cpu.py uses for svae.h; the header adds no constant and no struct; its table is disjoint from all others;
     the loaded library has every entry with the table's types, and ops._POINTER_ARGS knows the device pointers."""
     from spatial_vae_amd import _lib
     path = os.path.join(ROOT, "include", "svae_frc.h")
@@ -29,9 +29,9 @@ def test_frc_binding_matches_its_header():
     H = parse_header(text.replace('#include "svae.h"', ""))
     assert H["constants"] == {} and not H["structs"] and len(H["functions"]) == 4
     assert set(H["functions"]) == set(_lib.FRC_SIGNATURES) == set(_lib.declared_in_header(path))
-    tables = [set(_lib.SIGNATURES), set(_lib.STREAM_SIGNATURES), set(_lib.ALIGN_SIGNATURES), set(_lib.CTFCORR_SIGNATURES),
-              set(_lib.CLUSTER_SIGNATURES), set(_lib.FRC_SIGNATURES)]
-    assert all(not tables[i] & tables[j] for i in range(6) for j in range(i))
+    others = [t for h, t in _lib.HEADERS.items() if h != "svae_frc.h"]
+    assert _lib.HEADERS["svae_frc.h"] is _lib.FRC_SIGNATURES and len(others) == len(_lib.HEADERS) - 1
+    assert all(not set(t) & set(_lib.FRC_SIGNATURES) for t in others)
     for name, ((rbase, rptr), args) in H["functions"].items():
         restype, argtypes = _lib.FRC_SIGNATURES[name]
         assert restype in _allowed(rbase, rptr, _lib), name

@@ -26,7 +26,7 @@ def _infer():
 def test_gmm_binding_matches_its_header():
     """include/svae_gmm.h against _lib.GMM_SIGNATURES, both ways and type by type, with the parser and the type rules
     tests/test_binding_cpu.py uses for svae.h (`rec` is the address of a record in device memory: c_void_p); the header adds no
-    constant and one struct, whose mirror _lib.GmmRecord has its fields, size and offsets; the nine tables are pairwise disjoint;
+    constant and one struct, whose mirror _lib.GmmRecord has its fields, size and offsets; its table is disjoint from all others;
     the loaded library has every entry with the table's types, and ops._POINTER_ARGS knows the device pointers."""
     from spatial_vae_amd import _lib
     path = os.path.join(ROOT, "include", "svae_gmm.h")
@@ -35,10 +35,9 @@ def test_gmm_binding_matches_its_header():
     H = parse_header(text.replace('#include "svae.h"', ""))
     assert H["constants"] == {} and list(H["structs"]) == ["svae_gmm_record"] and len(H["functions"]) == 3
     assert set(H["functions"]) == set(_lib.GMM_SIGNATURES) == set(_lib.declared_in_header(path))
-    tables = [set(_lib.SIGNATURES), set(_lib.STREAM_SIGNATURES), set(_lib.ALIGN_SIGNATURES), set(_lib.CTFCORR_SIGNATURES),
-              set(_lib.CLUSTER_SIGNATURES), set(_lib.FRC_SIGNATURES), set(_lib.REFINE_SIGNATURES), set(_lib.CLASSIFY_SIGNATURES),
-              set(_lib.GMM_SIGNATURES)]
-    assert all(not tables[i] & tables[j] for i in range(9) for j in range(i))
+    others = [t for h, t in _lib.HEADERS.items() if h != "svae_gmm.h"]
+    assert _lib.HEADERS["svae_gmm.h"] is _lib.GMM_SIGNATURES and len(others) == len(_lib.HEADERS) - 1
+    assert all(not set(t) & set(_lib.GMM_SIGNATURES) for t in others)
     for name, ((rbase, rptr), args) in H["functions"].items():
         restype, argtypes = _lib.GMM_SIGNATURES[name]
         assert restype in _allowed(rbase, rptr, _lib), name

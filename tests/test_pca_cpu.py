@@ -1,7 +1,6 @@
 """CPU-only: the binding of include/svae_pca.h held to that header, the float64 reference of the PCA kernels (tests/pca_ref.py)
 held to numpy's own covariance and eigen-solver and to the conditions the GPU test relies on, infer.py's --pca options (their
 defaults and every refusal), elbo.traverse_latents against its formula, and the build's header check."""
-import inspect
 import os
 import subprocess
 import sys
@@ -26,8 +25,8 @@ def _infer():
 # ---------------------------------------------------------------- the header and its table
 def test_pca_binding_matches_its_header():
     """include/svae_pca.h against _lib.PCA_SIGNATURES, both ways and type by type, with the parser and the type rules
-    tests/test_binding_cpu.py uses for svae.h; the header adds no constant and no struct; the table is disjoint from the ten
-    others; the loaded library has every entry with the table's types, and ops._POINTER_ARGS knows the device pointers."""
+    tests/test_binding_cpu.py uses for svae.h; the header adds no constant and no struct; its table is disjoint from all others;
+    the loaded library has every entry with the table's types, and ops._POINTER_ARGS knows the device pointers."""
     from spatial_vae_amd import _lib, ops
     path = os.path.join(ROOT, "include", "svae_pca.h")
     with open(path) as f:
@@ -35,8 +34,8 @@ def test_pca_binding_matches_its_header():
     H = parse_header(text.replace('#include "svae.h"', ""))
     assert H["constants"] == {} and H["structs"] == {} and len(H["functions"]) == 4
     assert set(H["functions"]) == set(_lib.PCA_SIGNATURES) == set(_lib.declared_in_header(path))
-    others = [_lib.SIGNATURES, _lib.STREAM_SIGNATURES, _lib.ALIGN_SIGNATURES, _lib.CTFCORR_SIGNATURES, _lib.CLUSTER_SIGNATURES,
-              _lib.FRC_SIGNATURES, _lib.REFINE_SIGNATURES, _lib.CLASSIFY_SIGNATURES, _lib.GMM_SIGNATURES, _lib.EXPECT_SIGNATURES]
+    others = [t for h, t in _lib.HEADERS.items() if h != "svae_pca.h"]
+    assert _lib.HEADERS["svae_pca.h"] is _lib.PCA_SIGNATURES and len(others) == len(_lib.HEADERS) - 1
     assert all(not set(t) & set(_lib.PCA_SIGNATURES) for t in others)
     for name, ((rbase, rptr), args) in H["functions"].items():
         restype, argtypes = _lib.PCA_SIGNATURES[name]
@@ -291,12 +290,12 @@ def test_traverse_latents_against_the_formula():
 
 
 def test_the_build_checks_the_eleventh_header():
-    """__graft_entry__.build() holds include/svae_pca.h to _lib.PCA_SIGNATURES and resolves its names, and the library is stale
-    when that header is newer."""
-    import __graft_entry__ as entry
+    """__graft_entry__.build() walks _lib.HEADERS, so it holds include/svae_pca.h to _lib.PCA_SIGNATURES and resolves its names,
+    and the library is stale when that header is newer."""
     import spatial_vae_amd  # noqa: F401
+    from spatial_vae_amd import _lib
     build = sys.modules["spatial_vae_amd.build"]      # the module: the package's attribute of that name is its build()
-    text = inspect.getsource(entry.build)
-    assert '"svae_pca.h"' in text and "_lib.PCA_SIGNATURES" in text and "+ projecting" in text
-    assert '"svae_pca.h"' in inspect.getsource(build._stale)
-    assert os.path.isfile(os.path.join(ROOT, "include", "svae_pca.h"))
+    assert _lib.HEADERS["svae_pca.h"] is _lib.PCA_SIGNATURES
+    path = os.path.join(ROOT, "include", "svae_pca.h")
+    assert os.path.isfile(path)
+    assert any(os.path.samefile(path, d) for d in build.dependencies())
