@@ -1,8 +1,10 @@
 """Helper of tests/test_gpu_streams.py, tests/test_gpu_graph.py and tests/test_stream_cases_cpu.py (not collected): one table
-of enqueue-only callers, at least one per entry point of include/*.h that takes a stream.
+of enqueue-only callers, at least one per entry point of include/*.h that takes a stream.  A new header needs a row here (or in
+tests/stream_cases_analysis.py, which holds the rows of the analysis headers), not a test file of its own.
 
 A case knows three things.  inputs(seed): its input set as numpy arrays by name -- seed 0 (set A) and 1 (set B) have equal
-shapes and dtypes and different values; integer inputs (labels, quarter-turn codes, masks) are valid in both.  alloc(dev):
+shapes and dtypes and different values, but for the inputs the case names in same_in_both_sets; integer inputs (labels,
+quarter-turn codes, masks, reference and class indices) are valid in both.  alloc(dev):
 every device buffer its calls read or write -- the real inputs (case.real), a staging copy of each (case.stage), the outputs
 (case.outs, each inside guard bytes, the in-place ones listed in case.state too) and the scratch areas (case.scratch:
 workspaces, `saved`, records the calls initialise themselves).  steps(): the C-ABI calls in order, each a callable of the
@@ -10,7 +12,9 @@ stream handle that returns the call's status and does nothing else: no allocatio
 enqueue(stream) issues all of them.  Entry points that only make sense together are one case with several steps.
 
 Everything else here (load, poison, stage_to_real, collect) is what a test does AROUND the calls; none of it is called by
-enqueue.  The table is checked against the binding's signature tables by tests/test_stream_cases_cpu.py."""
+enqueue.  check(out, seed) holds a default-stream result to the case's reference; must_differ names the outputs that set B has
+to change.  The table is checked against _lib.ALL_SIGNATURES, the signature tables of every header, by
+tests/test_stream_cases_cpu.py."""
 import ctypes
 import math
 
@@ -29,10 +33,10 @@ NOT_CAPTURABLE = {}
 
 
 def stream_entry_points():
-    """Every function of the four signature tables whose last argument is the stream: it returns a status and its last argument
-    is a bare address (size queries return size_t; svae_profile_read ends in a typed pointer)."""
-    tables = {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES, **_lib.CTFCORR_SIGNATURES}
-    return sorted(name for name, (res, args) in tables.items() if res is _lib.cint and args and args[-1] is _lib.vp)
+    """Every function of _lib.ALL_SIGNATURES (one table per header of _lib.HEADERS) whose last argument is the stream: it
+    returns a status and its last argument is a bare address (size queries return size_t; svae_profile_read ends in a typed
+    pointer)."""
+    return sorted(name for name, (res, args) in _lib.ALL_SIGNATURES.items() if res is _lib.cint and args and args[-1] is _lib.vp)
 
 
 _TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
@@ -65,6 +69,9 @@ class Case(object):
     entry_points = ()
     state = ()                      # inputs the calls update in place: collected like outputs
     has_reference = False           # check(out) compares with float64 (else: finite, no sentinel, not constant)
+    same_in_both_sets = ()          # inputs that are deliberately equal in set A and set B (every other input differs)
+    must_differ = ()                # outputs that have to differ between the baselines of set A and set B
+    non_finite_inputs = ()          # float inputs that hold an inf or a NaN on purpose (every other one is finite in both sets)
 
     def inputs(self, seed):
         raise NotImplementedError
@@ -150,8 +157,9 @@ class Case(object):
         bad += [k for k, g in self.scratch.items() if not g.read()[1]]
         return out, bad
 
-    def check(self, out):
-        """The baseline is live: by default every output is finite, free of the sentinel and not constant."""
+    def check(self, out, seed=0):
+        """The baseline of input set `seed` is live: by default every output is finite, free of the sentinel and not constant.
+        A row whose check takes the seed is held to its reference on both sets; one that takes `out` alone, on set A."""
         for k, a in out.items():
             if a.dtype.kind == "f":
                 assert np.isfinite(a).all(), (self.name, k)
@@ -644,7 +652,7 @@ class Guard(Case):
     which must leave param, both moments and t alone."""
     name, entry_points = "guard_clip", ("svae_grad_guard_norm", "svae_adam_step_guarded")
     state = ("param", "grad", "exp_avg", "exp_avg_sq", "control")
-    may_be_constant = ("grad",)
+    may_be_constant = non_finite_inputs = ("grad",)
     n, max_norm, zero_grad = ADAM_N, 1.0, 1
 
     def inputs(self, seed, finite=None):
@@ -862,6 +870,10 @@ class PowerAndWiener(Case):
 CTF_LDS_PAIR = (10, 9)
 CTF_GLOBAL_PAIR = (88, 87)
 
+# the rows of the analysis headers (k-means, mixture, PCA, ring correlation, pose search, classification, soft averages) live in
+# a sibling file that subclasses Case, so it is imported here, below everything it needs
+from stream_cases_analysis import analysis_cases            # noqa: E402
+
 
 def make_cases():
     """Fresh, unallocated instances of every row of the table, in a fixed order."""
@@ -871,10 +883,11 @@ def make_cases():
     out += [Latent(), Latent(K=5), ElboHead(), IwHead(), IwStream(), Colsum(), Linear(17, 130, 33, "tanh"),
             Linear(5, 49, 24, "leakyrelu"), Adam(0), Adam(1), Guard(), Rotate(17, 1, False), Rotate(32, 3, True), CtfFilter(39),
             CtfFilter(81), AlignAndSums(), CtfApply(7, 10, 5), CtfApply(72, 72, 3), PowerAndWiener()]
-    return out
+    return out + analysis_cases()
 
 
 NAMES = [c.name for c in make_cases()]
+ANALYSIS_NAMES = [c.name for c in analysis_cases()]
 
 
 def make_case(name):

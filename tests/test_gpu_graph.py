@@ -22,7 +22,7 @@ import torch.nn as nn
 
 import stream_cases as S
 from decoder_abi import SENTINEL
-from test_gpu_streams import _dev, _handle, assert_bit_equal, assert_clean, baseline
+from test_gpu_streams import _dev, _eager, _fresh, _handle, assert_bit_equal, assert_clean, baseline
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,10 +75,7 @@ def test_every_case_under_replay(name):
     """Captured with input set A in its buffers: a replay equals baseline A; with set B written over the inputs in place, the
     eager default-stream result of B; a second replay of B the same again.  Scratch is NOT cleared in between: whatever the
     calls carry from one run to the next in their workspace, `saved` or a record would show."""
-    case = S.make_case(name).alloc(_dev())
-    case.load(0)
-    case.zero_scratch()
-    case.stage_to_real()
+    case = _fresh(name)
     g = _captured(case)
     assert_bit_equal(name, _replay(case, g), baseline(name), "replayed with set A")
     case.load(1)
@@ -86,24 +83,11 @@ def test_every_case_under_replay(name):
     assert_bit_equal(name, _replay(case, g), baseline(name, 1), "replayed with set B a second time")
 
 
-def _eager(case):
-    S.statuses_ok(case.enqueue(_handle(torch.cuda.current_stream())))
-    torch.cuda.synchronize()
-    out, bad = case.collect()
-    assert not bad
-    return out
-
-
 def test_the_guarded_pair_advances_its_count_inside_the_graph():
     """svae_grad_guard_norm -> svae_adam_step_guarded: three replays equal three eager call pairs, record included -- t,
     step_size and sqrt_bc2 live on the device and advance per replay.  A fourth replay on a gradient holding one inf leaves
     param, both moments and t alone, clears the gradient and counts a skipped step."""
-    cases = [S.Guard().alloc(_dev()) for _ in range(2)]
-    for c in cases:
-        c.load(0)
-        c.zero_scratch()
-        c.stage_to_real()
-    eager, graph = cases
+    cases = eager, graph = [_fresh("guard_clip") for _ in range(2)]
     g = _captured(graph)
     assert S.Guard.record(graph.collect()[0]["control"]).t == 3                 # the warm call was undone, the capture ran nothing
     rs = np.random.RandomState(5)
@@ -135,6 +119,64 @@ def test_the_guarded_pair_advances_its_count_inside_the_graph():
     rec = S.Guard.record(after["control"])
     assert rec.t == 6 and rec.apply == 0 and rec.finite == 0 and rec.skipped == 1 and rec.steps == 4
     assert (after["grad"] == 0).all()
+
+
+def test_kmeans_replays_advance_the_record_they_are_not_handed_afresh():
+    """One replay on set B and a zero record equals baseline B.  Replays WITHOUT restoring the record advance its count -- the
+    iterations live on the device -- and three of them equal three eager call sequences on one record, count included."""
+    name = "kmeans_N600_D3_k4"
+    case = _fresh(name)
+    g = _captured(case)
+    assert (case.collect()[0]["rec"] == 0).all()
+    assert_bit_equal(name, _replay(case, g), baseline(name), "replayed with set A")
+    case.load(1)                                    # set B, and the record back to zero bytes
+    assert_bit_equal(name, _replay(case, g), baseline(name, 1), "replayed with set B against the eager result of B")
+    for n in (2, 3):
+        g.replay()
+        torch.cuda.synchronize()
+        out, bad = case.collect()
+        assert not bad and out["rec"][0] == 2 * n, (n, out["rec"])
+        assert np.array_equal(out["seed_index"], baseline(name, 1)["seed_index"])
+    # the same calls made eagerly on a record that already counts: equal to the replays, count included
+    eager = _fresh(name, 1)
+    for _ in range(3):
+        want = _eager(eager)
+    assert_bit_equal(name, out, want, "three replays against three eager sequences")
+
+
+def test_the_mixture_steps_alone_in_a_second_graph():
+    """After one replay on set B (svae_gmm_init zeroes the record itself), a second graph holding one update step alone,
+    replayed twice on what the first left: the record's count advances to 3 and 4 -- the iterations live on the device -- and
+    everything equals the same calls made eagerly, which the reference confirms."""
+    import gmm_ref as G
+    from stream_cases_analysis import GMM_REG, GMM_TOL
+    name = "gmm_N600_D3_k4"
+    case = _fresh(name)
+    g = _captured(case)
+    assert (case.collect()[0]["rec"] == 0).all()
+    assert_bit_equal(name, _replay(case, g), baseline(name), "replayed with set A")
+    case.load(1)                                    # set B: x, label_in and the centres
+    assert_bit_equal(name, _replay(case, g), baseline(name, 1), "replayed with set B against the eager result of B")
+    one = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(one):
+        rc = case.step(1)(_handle(torch.cuda.current_stream()))
+    S.statuses_ok([rc])
+    torch.cuda.synchronize()
+    assert case.collect()[0]["rec"][0] == 2         # captured, not run
+    for n in (3, 4):
+        one.replay()
+        torch.cuda.synchronize()
+        out, bad = case.collect()
+        assert not bad and out["rec"][0] == n, (n, out["rec"])
+    eager = _fresh(name, 1)
+    _eager(eager)
+    want = _eager(eager, [eager.step(1), eager.step(1)])
+    assert_bit_equal(name, out, want, "two replayed steps against two eager ones")
+    ref = eager.inputs(1)
+    state = G.init(ref["x"], ref["label_in"], ref["mean"], GMM_REG)
+    for update in (1, 1, 0, 1, 1):
+        state = G.step(ref["x"], state, update, GMM_REG, GMM_TOL)
+    assert state["iterations"] == 4 and np.abs(out["mean"] - state["mean"]).max() <= 1e-10 * max(1.0, np.abs(state["mean"]).max())
 
 
 @pytest.mark.parametrize("zero_grad", [0, 1])

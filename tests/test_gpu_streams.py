@@ -5,7 +5,8 @@ other GPU test hands it the default stream, so a launch or a hipMemsetAsync that
 between two calls, would pass them all.  Here each case runs
 
   a. on a side stream behind a delay kernel, with its inputs, workspace and `saved` still poisoned while the host enqueues:
-     the real inputs arrive by copies queued on that same stream, so anything the library sent elsewhere has run on poison;
+     the real inputs arrive by copies queued on that same stream, so anything the library sent elsewhere has run on poison
+     (the analysis rows once more with the default stream held in a delay of its own, which no call may wait for);
   b. next to a second case on a second stream, the host calls interleaved;
 
 and must reproduce its default-stream baseline bit for bit.  The baseline itself is first held to the float64 reference and
@@ -23,6 +24,7 @@ one completes while the other sits in a delay kernel), and every test here uses 
 import contextlib
 import ctypes
 import functools
+import inspect
 import io
 import os
 import subprocess
@@ -100,17 +102,28 @@ def side_streams():
     pytest.fail("inconclusive: of 16 streams no two ran beside the default stream and each other (found %d)" % len(found))
 
 
-@functools.lru_cache(maxsize=None)
-def baseline(name, seed=0):
-    """The case's outputs from the default stream with input set `seed`, scratch zeroed; computed once and shared."""
+def _fresh(name, seed=0):
+    """The case allocated, input set `seed` in its staging copies and in its inputs, scratch zeroed."""
     case = S.make_case(name).alloc(_dev())
     case.load(seed)
     case.zero_scratch()
     case.stage_to_real()
-    S.statuses_ok(case.enqueue(_handle(torch.cuda.current_stream())))
+    return case
+
+
+def _eager(case, calls=None):
+    """The case's calls (or `calls`) on the current stream, synchronised: its outputs, nothing written outside them."""
+    S.statuses_ok([call(_handle(torch.cuda.current_stream())) for call in (case.steps() if calls is None else calls)])
     torch.cuda.synchronize()
     out, bad = case.collect()
-    assert not bad, (name, bad)
+    assert not bad, (case.name, bad)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def baseline(name, seed=0):
+    """The case's outputs from the default stream with input set `seed`, scratch zeroed; computed once and shared."""
+    out = _eager(_fresh(name, seed))
     for a in out.values():
         a.setflags(write=False)
     return out
@@ -157,12 +170,18 @@ def prepared(name):
 @pytest.mark.parametrize("name", S.NAMES)
 def test_the_default_stream_baseline_is_live(name):
     """Input set A on the default stream against the float64 reference and the bound of the case's own test file where one
-    exists (case.has_reference); elsewhere finite, free of the sentinel and not constant.  Set B gives other numbers."""
+    exists (case.has_reference); elsewhere finite, free of the sentinel and not constant.  A check that takes the seed (every
+    row of tests/stream_cases_analysis.py) holds set B to its reference too.  Set B gives other numbers, in every output the
+    case names in must_differ."""
     case = S.make_case(name)
     out = baseline(name)
     case.check({k: np.array(v) for k, v in out.items()})
     other = baseline(name, 1)
+    if "seed" in inspect.signature(case.check).parameters:
+        case.check({k: np.array(v) for k, v in other.items()}, seed=1)
     assert any(not np.array_equal(out[k], other[k]) for k in out), name
+    for k in case.must_differ:
+        assert not np.array_equal(out[k], other[k]), (name, k)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -171,8 +190,8 @@ def test_the_default_stream_baseline_is_live(name):
 @pytest.mark.parametrize("name", S.NAMES)
 def test_late_producer_on_a_side_stream(name):
     """The case behind a delay on a side stream, everything it reads poisoned until copies on that stream replace it.
-    MI355X: all 32 cases equal their baseline (the rank1_tanh decoder case also in the fp16x3 child); with svae_colsum's
-    launch moved to stream 0 in a scratch build the colsum case differs in 131 of 132 bytes."""
+    MI355X: every case of S.NAMES equals its baseline (the rank1_tanh decoder case also in the fp16x3 child); with
+    svae_colsum's launch moved to stream 0 in a scratch build the colsum case differs in 131 of 132 bytes."""
     want = baseline(name)
     delay_cycles()
     case = prepared(name)
@@ -185,6 +204,30 @@ def test_late_producer_on_a_side_stream(name):
     S.statuses_ok(rcs)
     s.synchronize()
     assert still_pending, "inconclusive: the %g ms delay had already run out when the last call returned" % DELAY_MS
+    out, bad = case.collect()
+    assert_clean(case, out, bad)
+    assert_bit_equal(name, out, want, "on a side stream")
+
+
+@pytest.mark.parametrize("name", S.ANALYSIS_NAMES)
+def test_on_a_side_stream_while_the_default_stream_is_busy(name):
+    """As above, with the default stream in a delay kernel of its own that is still running when the last call returns: no
+    call waited on the null stream or synchronised with it."""
+    want = baseline(name)
+    delay_cycles()
+    case = prepared(name)
+    s = side_streams()[0]
+    torch.cuda._sleep(delay_cycles())               # the default stream is busy
+    busy = torch.cuda.Event()
+    busy.record()
+    behind_a_delay(case, s)
+    rcs = case.enqueue(_handle(s))
+    done = torch.cuda.Event()
+    done.record(s)
+    still_pending = not done.query() and not busy.query()
+    S.statuses_ok(rcs)
+    torch.cuda.synchronize()
+    assert still_pending, "inconclusive: the %g ms delays had already run out when the last call returned" % DELAY_MS
     out, bad = case.collect()
     assert_clean(case, out, bad)
     assert_bit_equal(name, out, want, "on a side stream")

@@ -10,14 +10,13 @@ from spatial_vae_amd import _lib
 
 
 def test_the_table_covers_exactly_the_entry_points_that_take_a_stream():
-    """The names are derived from the binding's four signature tables (status returned, last argument a bare address), never
-    typed: a new export that takes a stream fails here until it has a case."""
+    """The names are derived from _lib.ALL_SIGNATURES, the signature tables of every header of _lib.HEADERS (status returned,
+    last argument a bare address), never typed: a new export that takes a stream fails here until it has a case."""
     derived = S.stream_entry_points()
-    assert len(derived) >= 28 and "svae_decoder_backward" in derived and "svae_wiener_finish" in derived
+    assert len(derived) >= 42 and "svae_decoder_backward" in derived and "svae_wiener_finish" in derived
     assert "svae_profile_read" not in derived and "svae_saved_bytes" not in derived
     assert S.covered_entry_points() == derived
-    tables = {**_lib.SIGNATURES, **_lib.STREAM_SIGNATURES, **_lib.ALIGN_SIGNATURES, **_lib.CTFCORR_SIGNATURES}
-    assert set(derived) <= set(tables)
+    assert set(derived) <= set(_lib.ALL_SIGNATURES)
     assert len(set(S.NAMES)) == len(S.NAMES)
 
 
@@ -32,14 +31,18 @@ def test_both_input_sets_have_one_layout_and_different_values(name):
     case = S.make_case(name)
     a, b = case.inputs(0), case.inputs(1)
     assert list(a) == list(b) and a
+    assert set(case.same_in_both_sets) < set(a), "every input is the same in both sets"
     for k in a:
         assert a[k].shape == b[k].shape and a[k].dtype == b[k].dtype, k
         assert a[k].dtype in (np.float32, np.float64, np.int32, np.int64, np.uint8), (k, a[k].dtype)
-        if a[k].dtype.kind == "f" and k != "grad":          # the guard's set B holds one inf on purpose
-            assert np.isfinite(a[k]).all() and np.isfinite(b[k]).all(), k
-        assert not np.array_equal(a[k], b[k]), "%s: %s is the same in both sets" % (name, k)
+        if a[k].dtype.kind == "f":                          # finite, but for what a case holds on purpose (the guard's one inf)
+            assert (np.isfinite(a[k]).all() and np.isfinite(b[k]).all()) != (k in case.non_finite_inputs), k
+        if k in case.same_in_both_sets:                     # stated by the case: a mask, a candidate table, a zero record
+            assert np.array_equal(a[k], b[k]), "%s: %s differs between the sets" % (name, k)
+        else:
+            assert not np.array_equal(a[k], b[k]), "%s: %s is the same in both sets" % (name, k)
     again = case.inputs(0)
-    assert all(np.array_equal(a[k], again[k]) for k in a)
+    assert all(a[k].tobytes() == again[k].tobytes() for k in a)
     assert set(case.state) <= set(a)
 
 
@@ -53,6 +56,22 @@ def test_integer_inputs_are_valid_in_both_sets():
                 assert (i["label"] >= -1).all() and (i["label"] < case.n_classes).all()
             if "mask" in i:
                 assert set(i["mask"].tolist()) <= {0, 1} and i["mask"].any()
+            # the analysis headers give every int32 a meaning: an entry outside the live range is a point in no group, an image
+            # that is skipped, an empty slot or a reference folded into no class.  Each set holds live entries and, where the
+            # case means to exercise it, -1 and an entry past the range.
+            if "label_in" in i:                             # svae_gmm.h: the start's labels, every point in a class
+                assert (i["label_in"] >= 0).all() and (i["label_in"] < case.k).all()
+            if "group" in i:                                # svae_pca.h: outside [0, G) is no group
+                live = (i["group"] >= 0) & (i["group"] < case.G)
+                assert live.sum() >= 2 and -1 in i["group"] and (i["group"] >= case.G).any()
+            if "ref_index" in i:                            # svae_refine.h: outside [0, n_ref) is skipped
+                assert (i["ref_index"] >= -1).all() and (i["ref_index"] < case.n_ref).all() and -1 in i["ref_index"]
+            if "cand" in i:                                 # svae_classify.h, svae_expect.h: outside [0, n_ref) is an empty slot
+                live = (i["cand"] >= 0) & (i["cand"] < case.n_ref)
+                assert (i["cand"] >= -1).all() and -1 in i["cand"] and live.any(1).sum() == len(live) - 1
+            if "target" in i and i["target"].dtype == np.int32:     # svae_expect.h: outside [0, n_classes) is folded into no class
+                assert i["target"].shape == (case.n_ref,) and (i["target"] >= 0).all()
+                assert set(range(case.n_classes)) <= set(i["target"].tolist())
     g = S.Guard()
     assert np.isfinite(g.inputs(0)["grad"]).all() and np.isinf(g.inputs(1)["grad"]).sum() == 1
     assert np.isfinite(g.inputs(1, finite=True)["grad"]).all()
