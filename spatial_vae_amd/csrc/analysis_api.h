@@ -332,7 +332,7 @@ int svae_pose_search(const float* y, const double* ref, const double* weight, co
                                            svae_pose_search_workspace_bytes(B, rows, cols, C, A, S),
                                            "%d x %d x %d images with A=%d, S=%d", rows, cols, C, A, S))
             return rc;
-    const RefineGeo g{B, n_ref, rows, cols, C, A, S, A > 0 ? step : 0.0};
+    const PoseGeo g{B, n_ref, 1, rows, cols, C, A, S, A > 0 ? step : 0.0, 0.0};
     return launch_form("svae_pose_search", POSE_KERNEL(pose_search_kernel, interp, false), POSE_KERNEL(pose_search_kernel, interp, true), f,
                        static_cast<hipStream_t>(stream), y, ref, weight, reinterpret_cast<const int*>(ref_index), pose_in, g, pose_out, score,
                        reinterpret_cast<int*>(offset), scores, f.at(ws), (long)f.slice);
@@ -356,10 +356,10 @@ int svae_pose_classify(const float* y, const double* ref, const double* weight, 
                                        "%d references and %d x %d x %d images with M=%d", n_ref, rows, cols, C, M))
         return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const ClassifyGeo g{B, n_ref, M, rows, cols, C, A, S, A > 0 ? step : 0.0};
+    const PoseGeo g{B, n_ref, M, rows, cols, C, A, S, A > 0 ? step : 0.0, 0.0};
     double* norms = static_cast<double*>(ws);
     const auto first = [&] {
-        hipLaunchKernelGGL(classify_norms_kernel, dim3(n_ref), dim3(256), 0, st, ref, weight, rows * cols * C, C, norms);
+        hipLaunchKernelGGL(pose_norms_kernel<true>, dim3(n_ref), dim3(256), 0, st, ref, weight, rows * cols * C, C, norms);
     };
     return launch_form_after("svae_pose_classify", first, POSE_KERNEL(pose_classify_kernel, interp, false),
                              POSE_KERNEL(pose_classify_kernel, interp, true), f, st, y, ref, weight, reinterpret_cast<const int*>(cand),
@@ -559,10 +559,10 @@ int svae_pose_expect(const float* y, const double* ref, const double* weight, co
                                        "%d references and %d x %d x %d images with M=%d, A=%d, S=%d", n_ref, rows, cols, C, M, A, S))
         return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const ExpectGeo g{B, n_ref, M, rows, cols, C, A, S, A > 0 ? step : 0.0, inv_sigma2};
+    const PoseGeo g{B, n_ref, M, rows, cols, C, A, S, A > 0 ? step : 0.0, inv_sigma2};
     double* hn = static_cast<double*>(ws);
     const auto first = [&] {
-        hipLaunchKernelGGL(expect_norms_kernel, dim3(n_ref), dim3(256), 0, st, ref, weight, rows * cols * C, C, hn);
+        hipLaunchKernelGGL(pose_norms_kernel<false>, dim3(n_ref), dim3(256), 0, st, ref, weight, rows * cols * C, C, hn);
     };
     return launch_form_after("svae_pose_expect", first, POSE_KERNEL(pose_expect_kernel, interp, false),
                              POSE_KERNEL(pose_expect_kernel, interp, true), f, st, y, ref, weight, log_prior,

@@ -1,63 +1,25 @@
-// Maximum-likelihood class averages (include/svae_expect.h).  A prologue, one workgroup of 256 per reference, takes each
-// reference's h = sum weight * ref^2 once per call.  The main kernel runs one workgroup of 256 per image (SCRATCH: the grid strides
-// over the images) in two passes over the angles.  The first resamples the image into the plane P_k as classify.h does and
-// fills the log-weight volume L: each (slot, nine shifts) is one wave's call of classify_correlate, so every D is bit for bit the
+// Maximum-likelihood class averages (include/svae_expect.h).  A prologue (pose_norms_kernel<false>) takes each reference's
+// h = sum weight * ref^2 once per call.  The main kernel runs one workgroup of 256 per image (SCRATCH: the grid strides
+// over the images) in two passes over the angles.  The first resamples the image into the plane P_k and its coverage and
+// fills the log-weight volume L: each (slot, nine shifts) is one wave's call of pose_correlate, so every D is bit for bit the
 // numerator of svae_pose_classify's score.  Between the passes the workgroup finds the first maximum, the sum of exp(L - Lmax)
 // and the posterior p, which takes L's place.  The second pass resamples each angle again and adds p * Q into the image's
 // contribution rows: a thread owns (slot, pixel) with all its channels and the coverage, reads p as a broadcast, and carries
 // its running sums through global memory from one angle to the next (the same thread, so no atomics).  Plane, coverage and
 // volume stay in LDS, or in the workgroup's slice of the workspace above the LDS limit: the same arithmetic in the same order.
-// Doubles with contraction off.  tests/expect_ref.py is the float64 restatement the kernels are held to.
+// tests/expect_ref.py is the float64 restatement the kernels are held to.
 #pragma once
-#include "classify.h"
+#include "pose_core.h"
 
 namespace svae {
-
-struct ExpectGeo {
-    int B, n_ref, M, rows, cols, C, A, S;
-    double step, inv_sigma2;
-};
 
 constexpr int kExpectMaxSlots = 64;
 constexpr int kExpectFixed = 8 + kExpectMaxSlots / 2;    // doubles of LDS every form keeps: 8 of reduction space, the slot references
 
-// h[r] = sum over (pix, c) of (weight[pix] * ref[r, pix, c]) * ref[r, pix, c]: classify_norms_kernel's loop and block sum
-__global__ void __launch_bounds__(256) expect_norms_kernel(const double* __restrict__ ref, const double* __restrict__ weight, int NC,
-                                                            int C, double* __restrict__ h) {
-#pragma clang fp contract(off)
-    __shared__ double red[8];
-    const int tid = threadIdx.x;
-    const double* rp = ref + (long)blockIdx.x * NC;
-    double part = 0.0;
-    for (int e = tid; e < NC; e += 256) {
-        const double wr = weight ? weight[e / C] * rp[e] : rp[e];
-        part += wr * rp[e];
-    }
-    const double sum = refine_block_sum(part, red);
-    if (tid == 0) h[blockIdx.x] = sum;
-}
-
-// the image at angle k into the plane and its coverage (1.0 / 0.0); the caller's barrier publishes both
-template <bool CUBIC>
-__device__ __forceinline__ void expect_resample(const float* __restrict__ img, double th, double dx0, double dx1, int k, double step,
-                                                int h, int w, int C, double* __restrict__ plane, double* __restrict__ cov) {
-#pragma clang fp contract(off)
-    const double thk = th + (double)k * step;
-    const double c = cos(thk), s = sin(thk);
-    const int NC = h * w * C;
-    for (int e = threadIdx.x; e < NC; e += 256) {
-        const int pix = e / C, ch = e - pix * C;
-        const int jy = pix / w, jx = pix - jy * w;
-        bool covered;
-        plane[e] = align_sample<CUBIC>(img, c, s, dx0, dx1, jy, jx, ch, h, w, C, &covered);
-        if (ch == 0) cov[pix] = covered ? 1.0 : 0.0;
-    }
-}
-
 template <bool CUBIC, bool SCRATCH>
 __global__ void __launch_bounds__(256) pose_expect_kernel(const float* __restrict__ y, const double* __restrict__ ref,
                                                            const double* __restrict__ weight, const double* __restrict__ log_prior,
-                                                           const int* __restrict__ cand, const float* __restrict__ pose_in, ExpectGeo g,
+                                                           const int* __restrict__ cand, const float* __restrict__ pose_in, PoseGeo g,
                                                            const double* __restrict__ hn, double* __restrict__ contrib,
                                                            double* __restrict__ cover_w, double* __restrict__ class_post,
                                                            double* __restrict__ log_evidence, int* __restrict__ best,
@@ -67,7 +29,7 @@ __global__ void __launch_bounds__(256) pose_expect_kernel(const float* __restric
     const int h = g.rows, w = g.cols, C = g.C, M = g.M;
     const int N = h * w, NC = N * C;
     const int nA = 2 * g.A + 1, nS = 2 * g.S + 1, nQ = nS * nS, V = nA * nQ, MV = M * V;
-    const int G = (nQ + kClassifyShifts - 1) / kClassifyShifts;     // groups of nine shifts per (slot, angle)
+    const int G = (nQ + kPoseShifts - 1) / kPoseShifts;             // groups of nine shifts per (slot, angle)
     double* red = lds_expect;                                       // 4 doubles of the block sums / maxima, 4 of the maxima's indices
     int* slots = reinterpret_cast<int*>(lds_expect + 8);            // the reference of each live slot, -1 for a dead one
     double* plane = SCRATCH ? scratch + (long)blockIdx.x * slice : lds_expect + kExpectFixed;
@@ -94,20 +56,20 @@ __global__ void __launch_bounds__(256) pose_expect_kernel(const float* __restric
         if (!skip) {
             // ---- first pass: the log-weight volume
             for (int k = -g.A; k <= g.A; ++k) {
-                expect_resample<CUBIC>(img, th, dx0, dx1, k, g.step, h, w, C, plane, cov);
+                pose_resample<CUBIC, true>(img, th, dx0, dx1, k, g.step, h, w, C, plane, cov);
                 __syncthreads();
                 for (int it = wave; it < M * G; it += 4) {          // uniform over the wave
-                    const int j = it / G, q0 = (it - j * G) * kClassifyShifts;
+                    const int j = it / G, q0 = (it - j * G) * kPoseShifts;
                     const int r = slots[j];
                     if (r < 0) continue;
-                    const int count = min(kClassifyShifts, nQ - q0);
-                    double acc[kClassifyShifts];
-                    classify_correlate(plane, ref + (long)r * NC, weight, q0, 1, count, nS, g.S, h, w, C, lane, acc);
+                    const int count = min(kPoseShifts, nQ - q0);
+                    double acc[kPoseShifts];
+                    pose_correlate(plane, ref + (long)r * NC, weight, q0, 1, count, nS, g.S, h, w, C, lane, acc);
                     if (lane == 0) {
                         const double half_h = 0.5 * hn[r], lp = log_prior ? log_prior[r] : 0.0;
                         double* vk = vol + ((long)j * nA + (k + g.A)) * nQ + q0;
 #pragma unroll
-                        for (int t = 0; t < kClassifyShifts; ++t)
+                        for (int t = 0; t < kPoseShifts; ++t)
                             if (t < count) vk[t] = g.inv_sigma2 * (acc[t] - half_h) + lp;
                     }
                 }
@@ -156,7 +118,7 @@ __global__ void __launch_bounds__(256) pose_expect_kernel(const float* __restric
             double part = 0.0;
             for (int i = tid; i < MV; i += 256)
                 if (slots[i / V] >= 0) part += exp(vol[i] - top_v);
-            Z = refine_block_sum(part, red);
+            Z = pose_block_sum(part, red);
             for (int i = tid; i < MV; i += 256)
                 if (slots[i / V] >= 0) vol[i] = exp(vol[i] - top_v) / Z;
             __syncthreads();
@@ -165,7 +127,7 @@ __global__ void __launch_bounds__(256) pose_expect_kernel(const float* __restric
                 if (slots[j] >= 0) {
                     const double* pj = vol + (long)j * V;
                     for (int i = lane; i < V; i += 64) s += pj[i];
-                    s = refine_wave_sum(s);
+                    s = pose_wave_sum(s);
                 }
                 if (lane == 0) class_post[(long)b * M + j] = s;
             }
@@ -181,7 +143,7 @@ __global__ void __launch_bounds__(256) pose_expect_kernel(const float* __restric
             }
             // ---- second pass: the contributions, each (slot, pixel) one thread's running sums
             for (int k = -g.A; k <= g.A; ++k) {
-                expect_resample<CUBIC>(img, th, dx0, dx1, k, g.step, h, w, C, plane, cov);
+                pose_resample<CUBIC, true>(img, th, dx0, dx1, k, g.step, h, w, C, plane, cov);
                 __syncthreads();
                 for (int t = tid; t < M * N; t += 256) {
                     const int j = t / N, pix = t - j * N;

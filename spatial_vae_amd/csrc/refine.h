@@ -1,40 +1,13 @@
 // Reference-based pose search (include/svae_refine.h).  One workgroup of 256 per image (SCRATCH: the grid strides over the
-// images).  Per angle the image is resampled once into the plane P_k, as doubles, by align.h's align_sample; the (2S+1)^2
-// shifted correlations with weight * ref are then shared over the four waves, one shift per wave at a time, the lanes striding
-// over the pixels and a butterfly closing each sum.  The image's score volume stays beside the plane (LDS, or the
-// workgroup's slice of the workspace above the LDS limit: the same arithmetic in the same order); the winner and the three
-// parabolas are thread 0's work at the end.  Doubles with contraction off, no atomics.  tests/refine_ref.py is the float64
-// restatement the kernel is held to.
+// images).  Per angle the image is resampled once into the plane P_k; its (2S+1)^2 shifted correlations with weight * ref are
+// pose_core.h's pose_correlate, the four waves sharing the shifts as classify.h's M < 4 branch does (wave, wave + 4, ...).  The
+// image's score volume stays beside the plane (LDS, or the workgroup's slice of the workspace above the LDS limit: the same
+// arithmetic in the same order); the winner and the three parabolas are thread 0's work at the end.  tests/refine_ref.py is
+// the float64 restatement the kernel is held to.
 #pragma once
-#include "align.h"
+#include "pose_core.h"
 
 namespace svae {
-
-struct RefineGeo {
-    int B, n_ref, rows, cols, C, A, S;
-    double step;
-};
-
-// the sum of v over the 64 lanes of the wave, the same bits in every lane (each level adds the two partners' values, and
-// IEEE addition commutes)
-__device__ __forceinline__ double refine_wave_sum(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// the sum of v over the 256 threads: waves first, then the four wave sums in index order.  Every thread gets the result;
-// `red` (4 doubles of LDS) is free again on return.
-__device__ __forceinline__ double refine_block_sum(double v, double* red) {
-#pragma clang fp contract(off)
-    v = refine_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double t = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return t;
-}
 
 // the sub-step offset of a winner with the neighbours l and r along one axis
 __device__ __forceinline__ double refine_parabola(double l, double c, double r) {
@@ -47,14 +20,14 @@ __device__ __forceinline__ double refine_parabola(double l, double c, double r) 
 template <bool CUBIC, bool SCRATCH>
 __global__ void __launch_bounds__(256) pose_search_kernel(const float* __restrict__ y, const double* __restrict__ ref,
                                                            const double* __restrict__ weight, const int* __restrict__ ref_index,
-                                                           const float* __restrict__ pose_in, RefineGeo g,
+                                                           const float* __restrict__ pose_in, PoseGeo g,
                                                            float* __restrict__ pose_out, double* __restrict__ score,
                                                            int* __restrict__ offset, double* __restrict__ scores,
                                                            double* __restrict__ scratch, long slice) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) double lds_refine[];
     const int N = g.rows * g.cols, NC = N * g.C;
-    const int nA = 2 * g.A + 1, nS = 2 * g.S + 1, V = nA * nS * nS;
+    const int nA = 2 * g.A + 1, nS = 2 * g.S + 1, nQ = nS * nS, V = nA * nQ;
     double* red = lds_refine;                                   // 8 doubles: 4 of the block sums, 4 spare
     double* plane = SCRATCH ? scratch + (long)blockIdx.x * slice : lds_refine + 8;
     double* vol = plane + NC;
@@ -68,12 +41,7 @@ __global__ void __launch_bounds__(256) pose_search_kernel(const float* __restric
         const double* rp = ref + (long)(skip ? 0 : r) * NC;
         double ref_sq = 0.0;
         if (!skip) {
-            double part = 0.0;
-            for (int e = tid; e < NC; e += 256) {
-                const double wr = weight ? weight[e / C] * rp[e] : rp[e];
-                part += wr * wr;
-            }
-            ref_sq = refine_block_sum(part, red);
+            ref_sq = pose_ref_sum<true>(rp, weight, NC, C, red);
             skip = ref_sq == 0.0;
         }
         if (skip) {
@@ -82,37 +50,17 @@ __global__ void __launch_bounds__(256) pose_search_kernel(const float* __restric
             const double ref_norm = sqrt(ref_sq);
             const float* img = y + (long)b * NC;
             for (int k = -g.A; k <= g.A; ++k) {
-                const double thk = th + (double)k * g.step;
-                const double c = cos(thk), s = sin(thk);
-                double part = 0.0;
-                for (int e = tid; e < NC; e += 256) {
-                    const int pix = e / C, ch = e - pix * C;
-                    const int jy = pix / w, jx = pix - jy * w;
-                    bool covered;
-                    const double v = align_sample<CUBIC>(img, c, s, dx0, dx1, jy, jx, ch, h, w, C, &covered);
-                    plane[e] = v;
-                    part += v * v;
-                }
-                const double p_sq = refine_block_sum(part, red);        // its barriers also publish the plane
+                const double part = pose_resample<CUBIC, false>(img, th, dx0, dx1, k, g.step, h, w, C, plane, nullptr);
+                const double p_sq = pose_block_sum(part, red);          // its barriers also publish the plane
                 const double denom = ref_norm * sqrt(p_sq);
-                double* vk = vol + (k + g.A) * nS * nS;
-                for (int q = wave; q < nS * nS; q += 4) {               // uniform over the wave
-                    const int sy = q / nS - g.S, sx = q - (q / nS) * nS - g.S;
-                    double acc = 0.0;
-                    for (int pix = lane; pix < N; pix += 64) {
-                        const int jy = pix / w, jx = pix - jy * w;
-                        const int yy = jy + sy, xx = jx - sx;
-                        if (yy < 0 || yy >= h || xx < 0 || xx >= w) continue;
-                        const double wt = weight ? weight[pix] : 1.0;
-                        const double* src = plane + ((long)yy * w + xx) * C;
-                        const double* rr = rp + (long)pix * C;
-                        for (int ch = 0; ch < C; ++ch) {
-                            const double wr = weight ? wt * rr[ch] : rr[ch];
-                            acc += wr * src[ch];
-                        }
-                    }
-                    acc = refine_wave_sum(acc);
-                    if (lane == 0) vk[q] = p_sq == 0.0 ? 0.0 : acc / denom;
+                double* vk = vol + (k + g.A) * nQ;
+                for (int q0 = wave; q0 < nQ; q0 += 4 * kPoseShifts) {   // this wave's shifts: wave, wave + 4, ...
+                    const int count = min(kPoseShifts, (nQ - q0 + 3) / 4);
+                    double acc[kPoseShifts];
+                    pose_correlate(plane, rp, weight, q0, 4, count, nS, g.S, h, w, C, lane, acc);
+#pragma unroll
+                    for (int t = 0; t < kPoseShifts; ++t)
+                        if (lane == 0 && t < count) vk[q0 + 4 * t] = p_sq == 0.0 ? 0.0 : acc[t] / denom;
                 }
                 __syncthreads();    // the waves have finished with the plane before the next angle overwrites it
             }

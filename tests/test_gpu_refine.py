@@ -20,8 +20,10 @@ TOL_POSE = 1e-6
 # (rows, cols, C, A, step, S, weighted).  The first two stay in LDS (8 (rows cols C + (2A+1)(2S+1)^2 + 8) bytes within 160 KiB);
 # 71 x 72 x 4 = 20448 doubles of plane with a volume of 45 is the smallest box of four channels that does not (71 x 71 x 4 =
 # 20164 does: 20164 + 45 + 8 <= 20480 < 20448 + 45 + 8) and goes through the workspace; the last has the largest search the
-# header takes, 65 angles by 17 x 17 shifts, most of which move the whole 9 x 8 box out of itself.
-SHAPES = [(24, 24, 1, 3, 0.05, 2, True), (17, 13, 3, 2, 0.08, 3, False), (71, 72, 4, 2, 0.03, 1, True), (9, 8, 1, 32, 0.02, 8, False)]
+# header takes, 65 angles by 17 x 17 shifts, most of which move the whole 9 x 8 box out of itself; the row after it is a volume of
+# one entry (A = S = 0): three of the four waves get no shift, no edge flag can be set and the reference's margin is +inf.
+SHAPES = [(24, 24, 1, 3, 0.05, 2, True), (17, 13, 3, 2, 0.08, 3, False), (71, 72, 4, 2, 0.03, 1, True), (9, 8, 1, 32, 0.02, 8, False),
+          (9, 8, 1, 0, 0.1, 0, True)]
 REF_INDEX = np.array([0, 1, -1, 2, 1], np.int32)        # two references, one image in no class, one all-zero reference
 
 
