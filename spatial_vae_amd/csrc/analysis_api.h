@@ -141,12 +141,6 @@ size_t norms_and_slices_bytes(int n_ref, const PlaneForm& f) {
 bool latent_sizes_ok(int64_t N, int32_t D, int32_t k) {
     return D >= 1 && D <= kKmeansMaxD && k >= 1 && k <= kKmeansMaxK && N >= k && N <= 0x7fffffffLL;
 }
-// the chunks of P points the kernels' grids walk (kmeans_chunk)
-struct Chunks {
-    long P;
-    int n;
-    explicit Chunks(int64_t N) : P(kmeans_chunk((long)N)), n((int)(((long)N + P - 1) / P)) {}
-};
 // f(std::integral_constant<int, DMAX>) for the kernels' DMAX of D coordinates in registers
 template <class F>
 void by_dim(int D, F f) {
@@ -378,7 +372,7 @@ int svae_kmeans_seed(const float* x, int64_t N, int32_t D, int32_t k, const doub
     if (misaligned8(u) || misaligned8(centres)) return fail(SVAE_E_INVALID, "svae_kmeans_seed: u and centres must be 8-byte aligned");
     if (const int rc = latent_check("svae_kmeans_seed", N, D, k, kmeans_ws_words, ws, ws_bytes)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Chunks ch(N);
+    const LatentChunks ch((long)N);
     const KmeansWs w = kmeans_ws(ws, (long)N, D, k);
     Scope prof(K_AUGMENT, st);
     for (int j = 0; j < k; ++j) {
@@ -401,7 +395,7 @@ int svae_kmeans_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t up
         return fail(SVAE_E_INVALID, "svae_kmeans_step: centres, members and rec must be 8-byte aligned");
     if (const int rc = latent_check("svae_kmeans_step", N, D, k, kmeans_ws_words, ws, ws_bytes)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Chunks ch(N);
+    const LatentChunks ch((long)N);
     const KmeansWs w = kmeans_ws(ws, (long)N, D, k);
     const int up = update ? 1 : 0;
     const long long* iterations = reinterpret_cast<const long long*>(&rec->iterations);
@@ -440,7 +434,7 @@ int svae_gmm_init(const float* x, int64_t N, int32_t D, int32_t k, const int32_t
     if (const int rc = gmm_check("svae_gmm_init", x, N, D, k, label_in, reg, 0.0, weight, mean, var, resp, nullptr, rec, ws, ws_bytes))
         return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Chunks ch(N);
+    const LatentChunks ch((long)N);
     const GmmWs w = gmm_ws(ws, (long)N, D, k);
     Scope prof(K_AUGMENT, st);
     hipLaunchKernelGGL(gmm_onehot_kernel, dim3(ch.n), dim3(256), 0, st, x, (long)N, D, k, ch.P, reinterpret_cast<const int*>(label_in), resp,
@@ -458,7 +452,7 @@ int svae_gmm_step(const float* x, int64_t N, int32_t D, int32_t k, int32_t updat
     if (const int rc = gmm_check("svae_gmm_step", x, N, D, k, label, reg, tol, weight, mean, var, resp, loglik_point, rec, ws, ws_bytes))
         return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Chunks ch(N);
+    const LatentChunks ch((long)N);
     const GmmWs w = gmm_ws(ws, (long)N, D, k);
     int* lab = reinterpret_cast<int*>(label);
     Scope prof(K_AUGMENT, st);
@@ -492,7 +486,7 @@ int svae_pca_moments(const float* x, int64_t N, int32_t D, int32_t G, const int3
                                        "N=%lld points with D=%d, G=%d", (long long)N, D, G))
         return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Chunks ch(N);
+    const LatentChunks ch((long)N);
     const PcaWs w = pca_ws(ws, (long)N, D, G);
     long long* cnt = reinterpret_cast<long long*>(count);
     Scope prof(K_AUGMENT, st);

@@ -1,22 +1,15 @@
 // k-means over (N, D) float points with (k, D) double centres (include/svae_cluster.h): k-means++ seeding and Lloyd steps.
 // The distance, the tie rule and the two-level order of every sum are stated in the header; tests/kmeans_ref.py is the float64
 // restatement the kernels are held to, bit for bit.  Doubles with contraction off, no atomics, no scratch: a point's
-// coordinates sit in registers (loops unrolled to the template bound DMAX and predicated on D), the centres in LDS.
+// coordinates sit in registers (loops unrolled to the template bound DMAX and predicated on D), the centres in LDS.  The
+// chunks, the point and the order of the sums are latent_core.h's, shared with gmm.h and pca.h.
 #pragma once
-#include "common.h"
+#include "latent_core.h"
 
 namespace svae {
 
-constexpr int kKmeansSlab = 4096;       // doubles of centres staged in LDS at a time (32 KiB)
 constexpr int kKmeansMaxD = 64;
 constexpr int kKmeansMaxK = 1024;
-
-// the chunk length of every reduction over points: svae_grad_guard_norm's rule on N
-__host__ __device__ inline long kmeans_chunk(long n) {
-    long c = 256;
-    while ((n + c - 1) / c > 1024) c *= 2;
-    return c;
-}
 
 // where the pieces of the workspace start, in 8-byte words
 struct KmeansWs {
@@ -29,12 +22,12 @@ struct KmeansWs {
 };
 
 __host__ __device__ inline size_t kmeans_ws_words(long N, int D, int k) {
-    const long P = kmeans_chunk(N), C = (N + P - 1) / P;
-    return (size_t)N + 3 * (size_t)C + (size_t)C * k + (size_t)C * k * D;
+    const size_t C = LatentChunks(N).n;
+    return (size_t)N + 3 * C + C * k + C * k * D;
 }
 
 inline KmeansWs kmeans_ws(void* ws, long N, int D, int k) {
-    const long P = kmeans_chunk(N), C = (N + P - 1) / P;
+    const long C = LatentChunks(N).n;
     KmeansWs w;
     w.dmin = static_cast<double*>(ws);
     w.inertia = w.dmin + N;
@@ -43,20 +36,6 @@ inline KmeansWs kmeans_ws(void* ws, long N, int D, int k) {
     w.count = w.assigned + C;
     w.part = reinterpret_cast<double*>(w.count + C * k);
     return w;
-}
-
-template <int DMAX>
-__device__ __forceinline__ bool kmeans_load_point(const float* __restrict__ x, long i, int D, float (&xr)[DMAX]) {
-    bool finite = true;
-#pragma unroll
-    for (int t = 0; t < DMAX; ++t) {
-        xr[t] = 0.0f;
-        if (t < D) {
-            xr[t] = x[i * D + t];
-            finite = finite && isfinite(xr[t]);
-        }
-    }
-    return finite;
 }
 
 // d2 of the header against the D doubles at c (LDS: every lane reads the same address, a broadcast)
@@ -81,72 +60,45 @@ __device__ __forceinline__ long kmeans_fallback(double u, long N) {
 }
 
 // Assign: one workgroup per chunk, 256 points per round, one thread per point.  The labels go out, and per chunk the in-order
-// sum of the winning distances (thread 0 walks the round's 256 values in LDS) and the changed / assigned counts.
+// sum of the winning distances and the changed / assigned counts (RoundFold).
 template <int DMAX>
 __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restrict__ x, long N, int D, int k, long P,
                                                             const double* __restrict__ centres, int* __restrict__ label,
                                                             const long long* __restrict__ iterations, KmeansWs w) {
 #pragma clang fp contract(off)
-    __shared__ double sc[kKmeansSlab];
-    __shared__ double sd[256];
-    __shared__ int sflag[256];
     const int tid = threadIdx.x;
-    const long lo = (long)blockIdx.x * P;
-    const long hi = lo + P < N ? lo + P : N;
+    const ChunkSpan span(blockIdx.x, P, N);
     const bool first = *iterations == 0;
-    const int per = kKmeansSlab / D;        // whole centres per slab
-    double inertia = 0.0;
-    long long changed = 0, assigned = 0;
-    for (long r0 = lo; r0 < hi; r0 += 256) {
+    RoundFold fold;     // sum: inertia; bit 0: assigned, bit 1: changed
+    for (long r0 = span.lo; r0 < span.hi; r0 += 256) {
         const long i = r0 + tid;
-        const bool live = i < hi;
+        const bool live = i < span.hi;
         float xr[DMAX];
-        bool finite = false;
-        if (live) finite = kmeans_load_point<DMAX>(x, i, D, xr);
-        else {
-#pragma unroll
-            for (int t = 0; t < DMAX; ++t) xr[t] = 0.0f;
-        }
+        const bool finite = point_load<DMAX>(x, i, live, D, xr);
         double best = 0.0;
         int bj = 0;
-        for (int j0 = 0; j0 < k; j0 += per) {
-            const int nj = k - j0 < per ? k - j0 : per;
-            __syncthreads();
-            for (int q = tid; q < nj * D; q += 256) sc[q] = centres[(long)j0 * D + q];
-            __syncthreads();
-            if (finite) {
-                for (int j = 0; j < nj; ++j) {
-                    const double d = kmeans_d2<DMAX>(xr, sc + j * D, D);
-                    if ((j0 == 0 && j == 0) || d < best) {
-                        best = d;
-                        bj = j0 + j;
-                    }
+        slab_walk(
+            k, D, finite, [&](int j, int t) { return centres[(long)j * D + t]; },
+            [&](int j, const double* c) {
+                const double d = kmeans_d2<DMAX>(xr, c, D);
+                if (j == 0 || d < best) {
+                    best = d;
+                    bj = j;
                 }
-            }
-        }
-        int flag = 0;       // bit 0: assigned, bit 1: changed
+            });
+        int flag = 0;
         if (live) {
             const int lab = finite ? bj : -1;
             const bool ch = first ? finite : label[i] != lab;
             label[i] = lab;
             flag = (finite ? 1 : 0) | (ch ? 2 : 0);
         }
-        sd[tid] = (live && finite) ? best : 0.0;
-        sflag[tid] = flag;
-        __syncthreads();
-        if (tid == 0) {
-            for (int q = 0; q < 256; ++q) inertia += sd[q];     // + 0 where no point won: exact, the values are >= 0
-        } else if (tid == 64) {
-            for (int q = 0; q < 256; ++q) {
-                assigned += sflag[q] & 1;
-                changed += (sflag[q] >> 1) & 1;
-            }
-        }
+        fold.add(best, flag);       // + 0 where no point won: exact, the values are >= 0
     }
-    if (tid == 0) w.inertia[blockIdx.x] = inertia;
+    if (tid == 0) w.inertia[blockIdx.x] = fold.sum;
     if (tid == 64) {
-        w.changed[blockIdx.x] = changed;
-        w.assigned[blockIdx.x] = assigned;
+        w.changed[blockIdx.x] = fold.n1;
+        w.assigned[blockIdx.x] = fold.n0;
     }
 }
 
@@ -156,15 +108,14 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float* __restr
 __global__ __launch_bounds__(256) void kmeans_accumulate_kernel(const float* __restrict__ x, long N, int D, int k, long P, int update,
                                                                 const int* __restrict__ label, KmeansWs w) {
 #pragma clang fp contract(off)
-    const long lo = (long)blockIdx.x * P;
-    const long hi = lo + P < N ? lo + P : N;
+    const ChunkSpan span(blockIdx.x, P, N);
     const int pairs = update ? k * D : k;
     for (int p = threadIdx.x; p < pairs; p += 256) {
         const int j = update ? p / D : p;
         const int t = update ? p - j * D : 0;
         double acc = 0.0;
         long long n = 0;
-        for (long i = lo; i < hi; ++i) {
+        for (long i = span.lo; i < span.hi; ++i) {
             if (label[i] != j) continue;
             if (update) acc += (double)x[i * D + t];
             n += 1;
@@ -180,52 +131,29 @@ __global__ __launch_bounds__(256) void kmeans_tail_kernel(int D, int k, int chun
                                                           long long* __restrict__ members, svae_kmeans_record* __restrict__ rec,
                                                           KmeansWs w) {
 #pragma clang fp contract(off)
-    __shared__ long long red[3][256];
     const int tid = threadIdx.x;
     const long g = (long)blockIdx.x * 256 + tid;
-    if (g < k) {
-        long long n = 0;
-        for (int c = 0; c < chunks; ++c) n += w.count[(long)c * k + g];
-        members[g] = n;
-    }
+    if (g < k) members[g] = chunk_total(w.count, chunks, k, g);
     if (update && g < (long)k * D) {
-        const int j = (int)(g / D), t = (int)(g - (long)j * D);
-        long long n = 0;
-        double s = 0.0;
-        for (int c = 0; c < chunks; ++c) {
-            n += w.count[(long)c * k + j];
-            s += w.part[((long)c * k + j) * D + t];
-        }
+        const long long n = chunk_total(w.count, chunks, k, g / D);
+        const double s = chunk_total(w.part, chunks, (long)k * D, g);
         if (n > 0) centres[g] = s / (double)n;
     }
     if (blockIdx.x != 0) return;
     long long empty = 0, changed = 0, assigned = 0;
-    for (int j = tid; j < k; j += 256) {
-        long long n = 0;
-        for (int c = 0; c < chunks; ++c) n += w.count[(long)c * k + j];
-        empty += n == 0;
-    }
+    for (int j = tid; j < k; j += 256) empty += chunk_total(w.count, chunks, k, j) == 0;
     for (int c = tid; c < chunks; c += 256) {
         changed += w.changed[c];
         assigned += w.assigned[c];
     }
-    red[0][tid] = empty;
-    red[1][tid] = changed;
-    red[2][tid] = assigned;
-    __syncthreads();
+    empty = block_sum(empty);
+    changed = block_sum(changed);
+    assigned = block_sum(assigned);
     if (tid != 0) return;
-    empty = changed = assigned = 0;
-    for (int q = 0; q < 256; ++q) {     // integers: any order gives the same number
-        empty += red[0][q];
-        changed += red[1][q];
-        assigned += red[2][q];
-    }
-    double inertia = 0.0;
-    for (int c = 0; c < chunks; ++c) inertia += w.inertia[c];
     rec->changed = changed;
     rec->assigned = assigned;
     rec->empty = empty;
-    rec->inertia = inertia;
+    rec->inertia = chunk_total(w.inertia, chunks, 1, 0);
     if (update) {
         const long long it = rec->iterations + 1;
         rec->iterations = it;
@@ -240,34 +168,27 @@ __global__ __launch_bounds__(256) void kmeans_seed_dist_kernel(const float* __re
                                                                const double* __restrict__ centres, int last, int first, KmeansWs w) {
 #pragma clang fp contract(off)
     __shared__ double sc[kKmeansMaxD];
-    __shared__ double sd[256];
     const int tid = threadIdx.x;
-    const long lo = (long)blockIdx.x * P;
-    const long hi = lo + P < N ? lo + P : N;
+    const ChunkSpan span(blockIdx.x, P, N);
     if (tid < D) sc[tid] = centres[(long)last * D + tid];
     __syncthreads();
-    double total = 0.0;
-    for (long r0 = lo; r0 < hi; r0 += 256) {
+    RoundFold fold;
+    for (long r0 = span.lo; r0 < span.hi; r0 += 256) {
         const long i = r0 + tid;
+        const bool live = i < span.hi;
+        float xr[DMAX];
         double m = 0.0;
-        if (i < hi) {
-            float xr[DMAX];
-            if (kmeans_load_point<DMAX>(x, i, D, xr)) {
-                m = kmeans_d2<DMAX>(xr, sc, D);
-                if (!first) {
-                    const double old = w.dmin[i];
-                    m = old < m ? old : m;
-                }
+        if (point_load<DMAX>(x, i, live, D, xr)) {
+            m = kmeans_d2<DMAX>(xr, sc, D);
+            if (!first) {
+                const double old = w.dmin[i];
+                m = old < m ? old : m;
             }
-            w.dmin[i] = m;
         }
-        sd[tid] = m;
-        __syncthreads();
-        if (tid == 0)
-            for (int q = 0; q < 256; ++q) total += sd[q];
-        __syncthreads();
+        if (live) w.dmin[i] = m;
+        fold.add(m, 0);
     }
-    if (tid == 0) w.inertia[blockIdx.x] = total;
+    if (tid == 0) w.inertia[blockIdx.x] = fold.sum;
 }
 
 // Seeding, the pick of centre j: one workgroup.  Thread 0 adds the chunk totals in order, finds the first chunk whose
@@ -286,8 +207,7 @@ __global__ __launch_bounds__(256) void kmeans_seed_pick_kernel(const float* __re
         s_chunk = -1;
         s_done = 0;
         if (j > 0) {
-            double T = 0.0;
-            for (int c = 0; c < chunks; ++c) T += w.inertia[c];
+            const double T = chunk_total(w.inertia, chunks, 1, 0);
             if (T > 0.0 && isfinite(T)) {
                 const double target = u[j] * T;
                 double pre = 0.0;
@@ -306,15 +226,14 @@ __global__ __launch_bounds__(256) void kmeans_seed_pick_kernel(const float* __re
     }
     __syncthreads();
     if (s_chunk >= 0) {         // uniform: every thread reads the same LDS word
-        const long lo = s_chunk * P;
-        const long hi = lo + P < N ? lo + P : N;
+        const ChunkSpan span(s_chunk, P, N);
         double run = 0.0;       // thread 0's running sum inside the chunk
-        for (long r0 = lo; r0 < hi; r0 += 256) {
+        for (long r0 = span.lo; r0 < span.hi; r0 += 256) {
             const long i = r0 + tid;
-            sd[tid] = i < hi ? w.dmin[i] : 0.0;
+            sd[tid] = i < span.hi ? w.dmin[i] : 0.0;
             __syncthreads();
             if (tid == 0) {
-                const int n = hi - r0 < 256 ? (int)(hi - r0) : 256;
+                const int n = span.hi - r0 < 256 ? (int)(span.hi - r0) : 256;
                 for (int q = 0; q < n; ++q) {
                     run += sd[q];
                     if (s_pre + run > s_target) {

@@ -1,6 +1,6 @@
-// Diagonal-covariance Gaussian mixture over (N, D) float points by EM (include/svae_gmm.h), a sibling of cluster.h: the same
-// chunk rule (kmeans_chunk), the same two-level order of every sum over points, a point's coordinates in registers and the
-// component parameters in LDS.  The arithmetic and its order are stated in the header; tests/gmm_ref.py is the float64
+// Diagonal-covariance Gaussian mixture over (N, D) float points by EM (include/svae_gmm.h), a sibling of cluster.h built from
+// the same latent_core.h: its chunk rule, its two-level order of every sum over points, a point's coordinates in registers and
+// the component parameters in LDS.  The arithmetic and its order are stated in the header; tests/gmm_ref.py is the float64
 // restatement the kernels are held to.  Doubles with contraction off, no atomics, no scratch.
 #pragma once
 #include "cluster.h"
@@ -20,17 +20,17 @@ struct GmmWs {
 };
 
 __host__ __device__ inline size_t gmm_ws_words(long N, int D, int k) {
-    const long P = kmeans_chunk(N), C = (N + P - 1) / P;
-    return (size_t)C * (2 + (size_t)k * (2 * D + 1)) + (size_t)k * (D + 1) + 4;
+    const size_t C = LatentChunks(N).n;
+    return C * (2 + (size_t)k * (2 * D + 1)) + (size_t)k * (D + 1) + 4;
 }
 
 inline GmmWs gmm_ws(void* ws, long N, int D, int k) {
-    const long P = kmeans_chunk(N), C = (N + P - 1) / P;
+    const size_t C = LatentChunks(N).n;
     GmmWs w;
     w.ll = static_cast<double*>(ws);
     w.assigned = reinterpret_cast<long long*>(w.ll + C);
     w.part = reinterpret_cast<double*>(w.assigned + C);
-    w.iv = w.part + (size_t)C * k * (2 * D + 1);
+    w.iv = w.part + C * k * (2 * D + 1);
     w.c = w.iv + (size_t)k * D;
     w.snap = reinterpret_cast<long long*>(w.c + k);
     return w;
@@ -83,54 +83,34 @@ __device__ __forceinline__ double gmm_score(const float (&xr)[DMAX], const doubl
 
 // E part: one workgroup per chunk, 256 points per round, one thread per point.  The scores a[i, :] are staged in the point's
 // row of resp while the slabs are walked, then read back twice: for s_i, and for the responsibilities written over them.  Per
-// chunk the in-order sum of ll_i (thread 0 walks the round's 256 values in LDS) and the assigned count.
+// chunk the in-order sum of ll_i and the assigned count (RoundFold).
 template <int DMAX>
 __global__ __launch_bounds__(256) void gmm_e_kernel(const float* __restrict__ x, long N, int D, int k, long P,
                                                     const double* __restrict__ mean, double* __restrict__ resp, int* __restrict__ label,
                                                     double* __restrict__ loglik_point, GmmWs w) {
 #pragma clang fp contract(off)
-    __shared__ double sc[kKmeansSlab];
-    __shared__ double sd[256];
-    __shared__ int sflag[256];
     const int tid = threadIdx.x;
-    const long lo = (long)blockIdx.x * P;
-    const long hi = lo + P < N ? lo + P : N;
-    const int width = 2 * D + 1;
-    const int per = kKmeansSlab / width;    // whole components per slab
-    double total = 0.0;
-    long long assigned = 0;
-    for (long r0 = lo; r0 < hi; r0 += 256) {
+    const ChunkSpan span(blockIdx.x, P, N);
+    RoundFold fold;     // sum: ll; bit 0: assigned
+    for (long r0 = span.lo; r0 < span.hi; r0 += 256) {
         const long i = r0 + tid;
-        const bool live = i < hi;
+        const bool live = i < span.hi;
         float xr[DMAX];
-        bool finite = false;
-        if (live) finite = kmeans_load_point<DMAX>(x, i, D, xr);
-        else {
-#pragma unroll
-            for (int t = 0; t < DMAX; ++t) xr[t] = 0.0f;
-        }
+        const bool finite = point_load<DMAX>(x, i, live, D, xr);
         double* row = resp + (live ? i : 0) * (long)k;
         double m = -INFINITY;
         int bj = 0;
-        for (int j0 = 0; j0 < k; j0 += per) {
-            const int nj = k - j0 < per ? k - j0 : per;
-            __syncthreads();
-            for (int q = tid; q < nj * width; q += 256) {
-                const int j = q / width, u = q - j * width;
-                sc[q] = u < D ? mean[(long)(j0 + j) * D + u] : u < 2 * D ? w.iv[(long)(j0 + j) * D + (u - D)] : w.c[j0 + j];
-            }
-            __syncthreads();
-            if (finite) {
-                for (int j = 0; j < nj; ++j) {
-                    const double a = gmm_score<DMAX>(xr, sc + j * width, D);
-                    row[j0 + j] = a;
-                    if (a > m) {
-                        m = a;
-                        bj = j0 + j;
-                    }
+        slab_walk(      // a staged component: mean (D), iv (D), c
+            k, 2 * D + 1, finite,
+            [&](int j, int u) { return u < D ? mean[(long)j * D + u] : u < 2 * D ? w.iv[(long)j * D + (u - D)] : w.c[j]; },
+            [&](int j, const double* comp) {
+                const double a = gmm_score<DMAX>(xr, comp, D);
+                row[j] = a;
+                if (a > m) {
+                    m = a;
+                    bj = j;
                 }
-            }
-        }
+            });
         const bool ok = finite && m > -INFINITY;    // a point no live component scores above -inf is unassigned too
         double ll = 0.0;
         if (ok) {
@@ -145,18 +125,10 @@ __global__ __launch_bounds__(256) void gmm_e_kernel(const float* __restrict__ x,
             label[i] = ok ? bj : -1;
             if (loglik_point) loglik_point[i] = ll;
         }
-        sd[tid] = ll;
-        sflag[tid] = ok ? 1 : 0;
-        __syncthreads();
-        if (tid == 0) {
-            for (int q = 0; q < 256; ++q) total += sd[q];       // + 0 where no point took part
-        } else if (tid == 64) {
-            for (int q = 0; q < 256; ++q) assigned += sflag[q];
-        }
-        __syncthreads();
+        fold.add(ll, ok ? 1 : 0);       // + 0 where no point took part
     }
-    if (tid == 0) w.ll[blockIdx.x] = total;
-    if (tid == 64) w.assigned[blockIdx.x] = assigned;
+    if (tid == 0) w.ll[blockIdx.x] = fold.sum;
+    if (tid == 64) w.assigned[blockIdx.x] = fold.n0;
 }
 
 // Init: the one-hot rows of label_in.  One workgroup per chunk; a thread per point finds its row's column (-1: an entry
@@ -164,34 +136,28 @@ __global__ __launch_bounds__(256) void gmm_e_kernel(const float* __restrict__ x,
 __global__ __launch_bounds__(256) void gmm_onehot_kernel(const float* __restrict__ x, long N, int D, int k, long P,
                                                          const int* __restrict__ label_in, double* __restrict__ resp, GmmWs w) {
     __shared__ int scol[256];
-    __shared__ int sflag[256];
     const int tid = threadIdx.x;
-    const long lo = (long)blockIdx.x * P;
-    const long hi = lo + P < N ? lo + P : N;
-    long long assigned = 0;
-    for (long r0 = lo; r0 < hi; r0 += 256) {
+    const ChunkSpan span(blockIdx.x, P, N);
+    RoundFold fold;     // bit 0: assigned
+    for (long r0 = span.lo; r0 < span.hi; r0 += 256) {
         const long i = r0 + tid;
         bool finite = false;
         int col = -1;
-        if (i < hi) {
-            finite = true;
-            for (int t = 0; t < D; ++t) finite = finite && isfinite(x[i * D + t]);
+        if (i < span.hi) {
+            finite = point_finite(x, i, D);
             const int lab = label_in[i];
             if (finite && lab >= 0 && lab < k) col = lab;
         }
         scol[tid] = col;
-        sflag[tid] = finite ? 1 : 0;
         __syncthreads();
-        const long n = hi - r0 < 256 ? hi - r0 : 256;
+        const long n = span.hi - r0 < 256 ? span.hi - r0 : 256;
         for (long q = tid; q < n * k; q += 256) {
             const int r = (int)(q / k);
             resp[r0 * k + q] = scol[r] == (int)(q - (long)r * k) ? 1.0 : 0.0;
         }
-        if (tid == 64)
-            for (int q = 0; q < 256; ++q) assigned += sflag[q];
-        __syncthreads();
+        fold.add(0.0, finite ? 1 : 0);      // its barriers keep the next round's scol from this round's readers
     }
-    if (tid == 64) w.assigned[blockIdx.x] = assigned;
+    if (tid == 64) w.assigned[blockIdx.x] = fold.n0;
 }
 
 // Accumulate: one workgroup per chunk, a thread per (component, t) pair with t in 0..D walking the chunk's points in index
@@ -203,15 +169,14 @@ __global__ __launch_bounds__(256) void gmm_accumulate_kernel(const float* __rest
                                                              const long long* __restrict__ frozen, GmmWs w) {
 #pragma clang fp contract(off)
     if (frozen && *frozen != 0) return;
-    const long lo = (long)blockIdx.x * P;
-    const long hi = lo + P < N ? lo + P : N;
+    const ChunkSpan span(blockIdx.x, P, N);
     const int width = 2 * D + 1;
     for (int p = threadIdx.x; p < k * (D + 1); p += 256) {
         const int j = p / (D + 1), t = p - j * (D + 1);
         double* out = w.part + ((long)blockIdx.x * k + j) * width;
         if (t == D) {
             double R = 0.0;
-            for (long i = lo; i < hi; ++i) {
+            for (long i = span.lo; i < span.hi; ++i) {
                 const double r = resp[i * k + j];
                 if (r == 0.0) continue;
                 R += r;
@@ -220,7 +185,7 @@ __global__ __launch_bounds__(256) void gmm_accumulate_kernel(const float* __rest
         } else {
             const double mu = mean[(long)j * D + t];
             double s1 = 0.0, s2 = 0.0;
-            for (long i = lo; i < hi; ++i) {
+            for (long i = span.lo; i < span.hi; ++i) {
                 const double r = resp[i * k + j];
                 if (r == 0.0) continue;
                 const double d = (double)x[i * D + t] - mu;
@@ -242,30 +207,15 @@ __global__ __launch_bounds__(256) void gmm_tail_kernel(int D, int k, int chunks,
                                                        double* __restrict__ weight, double* __restrict__ mean, double* __restrict__ var,
                                                        svae_gmm_record* __restrict__ rec, GmmWs w) {
 #pragma clang fp contract(off)
-    __shared__ long long red[256];
     __shared__ double s_ll;
-    __shared__ long long s_assigned;
     const int tid = threadIdx.x;
     const long g = (long)blockIdx.x * 256 + tid;
     const int width = 2 * D + 1;
     long long n = 0;
     for (int c = tid; c < chunks; c += 256) n += w.assigned[c];
-    red[tid] = n;
-    if (tid == 0) {
-        double ll = 0.0;
-        if (mode != kGmmInit)
-            for (int c = 0; c < chunks; ++c) ll += w.ll[c];
-        s_ll = ll;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        n = 0;
-        for (int q = 0; q < 256; ++q) n += red[q];      // integers: any order gives the same number
-        s_assigned = n;
-    }
-    __syncthreads();
+    if (tid == 0) s_ll = mode != kGmmInit ? chunk_total(w.ll, chunks, 1, 0) : 0.0;
+    const long long assigned = block_sum(n);        // its barriers publish s_ll too
     const double ll = s_ll;
-    const long long assigned = s_assigned;
     long long conv = 0, it = 0;
     bool apply = mode == kGmmInit;
     if (mode == kGmmStep) {
@@ -279,19 +229,12 @@ __global__ __launch_bounds__(256) void gmm_tail_kernel(int D, int k, int chunks,
     }
     if (apply && g < (long)k * (D + 1)) {
         const int j = (int)(g / (D + 1)), t = (int)(g - (long)j * (D + 1));
-        double R = 0.0, s1 = 0.0, s2 = 0.0;
-        for (int c = 0; c < chunks; ++c) {
-            const double* in = w.part + ((long)c * k + j) * width;
-            R += in[2 * D];
-            if (t < D) {
-                s1 += in[t];
-                s2 += in[D + t];
-            }
-        }
+        const long stride = (long)k * width, at = (long)j * width;
+        const double R = chunk_total(w.part, chunks, stride, at + 2 * D);
         if (t == D) weight[j] = R > 0.0 ? R / (double)assigned : 0.0;
         else if (R > 0.0) {
-            const double delta = s1 / R;
-            const double v = s2 / R - delta * delta;
+            const double delta = chunk_total(w.part, chunks, stride, at + t) / R;
+            const double v = chunk_total(w.part, chunks, stride, at + D + t) / R - delta * delta;
             mean[(long)j * D + t] = mean[(long)j * D + t] + delta;
             var[(long)j * D + t] = (v > 0.0 ? v : 0.0) + reg;
         }
@@ -299,20 +242,11 @@ __global__ __launch_bounds__(256) void gmm_tail_kernel(int D, int k, int chunks,
     if (blockIdx.x != 0) return;
     long long dead = 0;
     for (int j = tid; j < k; j += 256) {
-        if (apply) {
-            double R = 0.0;
-            for (int c = 0; c < chunks; ++c) R += w.part[((long)c * k + j) * width + 2 * D];
-            dead += !(R > 0.0);
-        } else {
-            dead += !(weight[j] > 0.0);
-        }
+        if (apply) dead += !(chunk_total(w.part, chunks, (long)k * width, (long)j * width + 2 * D) > 0.0);
+        else dead += !(weight[j] > 0.0);
     }
-    __syncthreads();
-    red[tid] = dead;
-    __syncthreads();
+    dead = block_sum(dead);
     if (tid != 0) return;
-    dead = 0;
-    for (int q = 0; q < 256; ++q) dead += red[q];
     if (mode == kGmmInit) {
         rec->iterations = 0;
         rec->converged_at = 0;

@@ -1,5 +1,5 @@
-// Principal axes of (N, D) float points, globally or per group (include/svae_pca.h), a sibling of cluster.h and gmm.h: the same
-// chunk rule (kmeans_chunk) and the same two-level order of every sum over points; the covariances are then diagonalised by
+// Principal axes of (N, D) float points, globally or per group (include/svae_pca.h), a sibling of cluster.h and gmm.h built from
+// the same latent_core.h: its chunk rule and its two-level order of every sum over points; the covariances are then diagonalised by
 // cyclic Jacobi, one workgroup per matrix with A and V in LDS.  The arithmetic and its order are stated in the header;
 // tests/pca_ref.py is the float64 restatement the kernels are held to.  Doubles with contraction off, no atomics, no scratch.
 #pragma once
@@ -27,17 +27,17 @@ struct PcaWs {
 };
 
 __host__ __device__ inline size_t pca_ws_words(long N, int D, int G) {
-    const long P = kmeans_chunk(N), C = (N + P - 1) / P;
-    return (size_t)C * G * (1 + D + D * (D + 1) / 2) + ((size_t)N + 1) / 2;
+    const size_t C = LatentChunks(N).n;
+    return C * G * (1 + D + D * (D + 1) / 2) + ((size_t)N + 1) / 2;
 }
 
 inline PcaWs pca_ws(void* ws, long N, int D, int G) {
-    const long P = kmeans_chunk(N), C = (N + P - 1) / P;
+    const size_t C = LatentChunks(N).n;
     PcaWs w;
     w.count = static_cast<long long*>(ws);
     w.sum = reinterpret_cast<double*>(w.count + C * G);
-    w.prod = w.sum + (size_t)C * G * D;
-    w.member = reinterpret_cast<int*>(w.prod + (size_t)C * G * (D * (D + 1) / 2));
+    w.prod = w.sum + C * G * D;
+    w.member = reinterpret_cast<int*>(w.prod + C * G * (D * (D + 1) / 2));
     return w;
 }
 
@@ -45,10 +45,17 @@ inline PcaWs pca_ws(void* ws, long N, int D, int G) {
 __device__ __forceinline__ int pca_member(const float* __restrict__ x, long i, int D, int G, const int* __restrict__ group) {
     const int g = group ? group[i] : 0;
     if (g < 0 || g >= G) return -1;
-    bool finite = true;
-    for (int t = 0; t < D; ++t) finite = finite && isfinite(x[i * D + t]);
-    return finite ? g : -1;
+    return point_finite(x, i, D) ? g : -1;
 }
+
+// entry e of a lower triangle stored row by row: (t, u <= t) with e = t (t + 1) / 2 + u
+struct PcaTri {
+    int t, u;
+    __device__ __forceinline__ explicit PcaTri(int e) : t(0) {
+        while ((t + 1) * (t + 2) / 2 <= e) ++t;
+        u = e - t * (t + 1) / 2;
+    }
+};
 
 // Pass 1: one workgroup per chunk.  A thread per point first writes the chunk's entries of w.member; then a thread per
 // (group, t) pair with t in 0..D walks the chunk's points in index order: the coordinate sum for t < D, the member count for
@@ -56,20 +63,19 @@ __device__ __forceinline__ int pca_member(const float* __restrict__ x, long i, i
 __global__ __launch_bounds__(256) void pca_sums_kernel(const float* __restrict__ x, long N, int D, int G, long P,
                                                        const int* __restrict__ group, PcaWs w) {
 #pragma clang fp contract(off)
-    const long lo = (long)blockIdx.x * P;
-    const long hi = lo + P < N ? lo + P : N;
-    for (long i = lo + threadIdx.x; i < hi; i += 256) w.member[i] = pca_member(x, i, D, G, group);
+    const ChunkSpan span(blockIdx.x, P, N);
+    for (long i = span.lo + threadIdx.x; i < span.hi; i += 256) w.member[i] = pca_member(x, i, D, G, group);
     __syncthreads();
     const int* member = w.member;
     for (int p = threadIdx.x; p < G * (D + 1); p += 256) {
         const int g = p / (D + 1), t = p - g * (D + 1);
         if (t == D) {
             long long n = 0;
-            for (long i = lo; i < hi; ++i) n += member[i] == g;
+            for (long i = span.lo; i < span.hi; ++i) n += member[i] == g;
             w.count[(long)blockIdx.x * G + g] = n;
         } else {
             double s = 0.0;
-            for (long i = lo; i < hi; ++i)
+            for (long i = span.lo; i < span.hi; ++i)
                 if (member[i] == g) s += (double)x[i * D + t];
             w.sum[((long)blockIdx.x * G + g) * D + t] = s;
         }
@@ -83,33 +89,28 @@ __global__ __launch_bounds__(256) void pca_mean_kernel(int D, int G, int chunks,
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= (long)G * (D + 1)) return;
     const int g = (int)(p / (D + 1)), t = (int)(p - (long)g * (D + 1));
-    long long n = 0;
-    for (int c = 0; c < chunks; ++c) n += w.count[(long)c * G + g];
+    const long long n = chunk_total(w.count, chunks, G, g);
     if (t == D) {
         count[g] = n;
         return;
     }
-    double s = 0.0;
-    for (int c = 0; c < chunks; ++c) s += w.sum[((long)c * G + g) * D + t];
-    mean[(long)g * D + t] = n > 0 ? s / (double)n : 0.0;
+    mean[(long)g * D + t] = n > 0 ? chunk_total(w.sum, chunks, (long)G * D, (long)g * D + t) / (double)n : 0.0;
 }
 
 // Pass 2: one workgroup per chunk, a thread per (group, t, u <= t) walking the chunk's points in index order.
 __global__ __launch_bounds__(256) void pca_products_kernel(const float* __restrict__ x, long N, int D, int G, long P,
                                                            const double* __restrict__ mean, PcaWs w) {
 #pragma clang fp contract(off)
-    const long lo = (long)blockIdx.x * P;
-    const long hi = lo + P < N ? lo + P : N;
+    const ChunkSpan span(blockIdx.x, P, N);
     const int T = D * (D + 1) / 2;
     const int* __restrict__ member = w.member;
     for (int p = threadIdx.x; p < G * T; p += 256) {
         const int g = p / T, e = p - g * T;
-        int t = 0;
-        while ((t + 1) * (t + 2) / 2 <= e) ++t;
-        const int u = e - t * (t + 1) / 2;
+        const PcaTri tri(e);
+        const int t = tri.t, u = tri.u;
         const double mt = mean[(long)g * D + t], mu = mean[(long)g * D + u];
         double m = 0.0;
-        for (long i = lo; i < hi; ++i)
+        for (long i = span.lo; i < span.hi; ++i)
             if (member[i] == g) {
                 const double dt = (double)x[i * D + t] - mt;
                 const double du = (double)x[i * D + u] - mu;
@@ -127,16 +128,10 @@ __global__ __launch_bounds__(256) void pca_cov_kernel(int D, int G, int chunks, 
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= (long)G * T) return;
     const int g = (int)(p / T), e = (int)(p - (long)g * T);
-    int t = 0;
-    while ((t + 1) * (t + 2) / 2 <= e) ++t;
-    const int u = e - t * (t + 1) / 2;
+    const PcaTri tri(e);
+    const int t = tri.t, u = tri.u;
     const long long n = count[g];
-    double v = 0.0;
-    if (n >= 2) {
-        double m = 0.0;
-        for (int c = 0; c < chunks; ++c) m += w.prod[((long)c * G + g) * T + e];
-        v = m / (double)(n - 1);
-    }
+    const double v = n >= 2 ? chunk_total(w.prod, chunks, (long)G * T, p) / (double)(n - 1) : 0.0;
     cov[((long)g * D + t) * D + u] = v;
     cov[((long)g * D + u) * D + t] = v;
 }

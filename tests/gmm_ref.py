@@ -157,7 +157,8 @@ def planted(seed, N, D, k):
 
 # The fixtures of the kernel tests: (seed, N, D, k, spread of the planted centres; 0.35 is the noise, so 0.6 overlaps).
 FIXTURES = [(0, 300, 3, 4, 2.0), (1, 257, 1, 2, 2.0), (2, 1000, 8, 6, 0.6), (3, 700, 5, 10, 0.6), (4, 513, 64, 3, 2.0),
-            (5, 600, 64, 32, 2.0), (6, 900, 8, 40, 2.0), (7, 262145, 2, 2, 2.0)]
+            (5, 600, 64, 32, 2.0), (6, 900, 8, 40, 2.0), (7, 262145, 2, 2, 2.0),
+            (8, 300, 4, 3, 2.0), (9, 300, 16, 3, 2.0), (10, 300, 17, 3, 2.0)]     # D on the 4 / 16 / 64 register bounds
 FIT_STEPS, FIT_REG, FIT_TOL = 25, 1e-6, 1e-6
 _cache = {}
 

@@ -91,14 +91,16 @@ def _min_gap(x, centres):
     return float(((d[:, 1] - d[:, 0]) / d[:, 1]).min()) if centres.shape[0] > 1 else 1.0
 
 
-BLOBS = [(0, 1000, 3, 5, 8), (1, 4097, 1, 2, 8), (2, 300, 8, 17, 8), (3, 257, 2, 3, 8), (4, 262145, 2, 3, 12), (5, 2048, 64, 1024, 3)]
+BLOBS = [(0, 1000, 3, 5, 8), (1, 4097, 1, 2, 8), (2, 300, 8, 17, 8), (3, 257, 2, 3, 8), (4, 262145, 2, 3, 12), (5, 2048, 64, 1024, 3),
+         (6, 300, 4, 3, 3), (7, 300, 5, 3, 3), (8, 300, 16, 3, 3), (9, 300, 17, 3, 3)]
 
 
 @pytest.mark.parametrize("seed,N,D,k,steps", BLOBS, ids=["N%d_D%d_k%d" % c[1:4] for c in BLOBS])
 def test_seed_and_every_step_equal_the_reference(seed, N, D, k, steps):
     """Blobs (kmeans_ref.blobs): the seeding's picks and centres, then `steps` update steps and one assign-only step, each held
     to the reference.  (4097, 1, 2) has 17 chunks, the last of one point; (262145, 2, 3) doubles the chunk to 512; (2048, 64,
-    1024) walks the centres in 16 slabs of 64.  MI355X: holds, bit for bit, in every shape."""
+    1024) walks the centres in 16 slabs of 64; D = 4, 5, 16, 17 sit on either side of the 4 / 16 / 64 register bounds, in two
+    chunks, the second of 44 points.  MI355X: holds, bit for bit, in every shape."""
     x, u = K.blobs(seed, N, D, k)
     run = Run(x, k)
     assert run.seed(u) == 0
