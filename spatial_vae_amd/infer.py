@@ -1,11 +1,11 @@
 """infer.py: apply a trained model to a dataset, one row per image (the root script infer.py is the entry point).
 
-Its own command line (infer_arguments: every refusal that needs no data, made before the kernel library is loaded), its file
-writers, and infer_main: a short sequence of stages -- load the model, check the request against the split, allocate the
-accumulators, walk the minibatches scoring (and aligning) them, cluster, take the principal axes of the content latents (--pca),
-refine the poses against the class averages (--refine;
-with --reassign also the classes),
-finish the half-set correlation (--frc), collect and
+The command line, the rules between its options, the rules against the model and the `meta` record are declared once, as
+tables, in infer_request.py (infer_arguments, check_request, run_meta: every refusal that needs no device, made before the
+kernel library is loaded); their names are importable from here as they always were.  This module holds the file writers and
+infer_main: a short sequence of stages -- load the model, check the request against the split, allocate the accumulators, walk
+the minibatches scoring (and aligning) them, cluster, take the principal axes of the content latents (--pca), refine the poses
+against the class averages (--refine; with --reassign also the classes), finish the half-set correlation (--frc), collect and
 write.  The device work is elbo.py's (score_minibatch, align_minibatch, reconstruct_unposed, cluster_latents, principal_axes,
 traverse_latents, refine_poses, classify_poses, frc_weight) and ops.py's.
 """
@@ -13,363 +13,29 @@ import collections
 import json
 import math
 import os
-import sys
 
 import numpy as np
 import torch
 
 from . import elbo as E
+from . import infer_request
 from . import ops
 from .cli import (SCRIPTS, RESUME_ARG_DEFAULTS, CheckpointError, check_resume_fingerprint, coord_grid, dataset_fingerprint,
                   pick_device, read_checkpoint)
+from .infer_request import (INFER_FRC_MAX_BOX, INFER_FRC_MAX_CLASSES, INFER_MAX_CHUNK, INFER_MAX_CLASSES,  # noqa: F401
+                            INFER_MAX_CLUSTERS, INFER_MAX_GMM_ITERS, INFER_MAX_GMM_RESP, INFER_MAX_PCA_PARTIALS,
+                            INFER_MAX_PCA_STEPS, INFER_MAX_REASSIGN_CLASSES, INFER_MAX_REFINE_ANGLES, INFER_MAX_REFINE_ROUNDS,
+                            INFER_MAX_REFINE_SHIFT, INFER_MAX_RESTARTS, INFER_MAX_SOFT_CLASSES, INFER_PATH_OVERRIDES,
+                            INFER_STACK_FORMATS, SplitFacts, _refuse, check_request, frc_mask_radius, read_labels, run_meta)
 
-INFER_MAX_CHUNK = 1024      # samples per image in one decoder call (the kernels' SVAE_IW_MAX_SAMPLES)
-INFER_PATH_OVERRIDES = ("train_path", "test_path", "ctf_train", "ctf_test")
-INFER_MAX_CLASSES = 4096    # classes of --labels (svae_class_sums_update's limit)
-INFER_STACK_FORMATS = (".npy", ".mrcs")
-INFER_MAX_CLUSTERS = min(INFER_MAX_CLASSES, 1024)   # classes of --cluster (include/svae_cluster.h's limit on k)
-INFER_MAX_RESTARTS = 16
-INFER_MAX_GMM_ITERS = 1000
-INFER_MAX_GMM_RESP = 2 ** 28        # images * K of --cluster_gmm: the (images, K) float64 responsibilities stay within 2 GiB
-INFER_FRC_MAX_CLASSES = INFER_MAX_CLASSES // 2      # --frc keeps two half-set sums per class
-INFER_FRC_MAX_BOX = 1024    # include/svae_frc.h's limit on n and m
 FRC_THRESHOLDS = (("resolution_0143", 0.143), ("resolution_05", 0.5))
-INFER_MAX_REFINE_ROUNDS = 10
-INFER_MAX_REFINE_ANGLES = 32    # include/svae_refine.h's limits on A and S
-INFER_MAX_REFINE_SHIFT = 8
-INFER_MAX_REASSIGN_CLASSES = 4096   # include/svae_classify.h's limit on M (2K slots never arise: a half sees its own K averages)
-INFER_MAX_SOFT_CLASSES = 64         # include/svae_expect.h's limit on M
-INFER_MAX_PCA_STEPS = 50
-INFER_MAX_PCA_PARTIALS = 32768      # include/svae_pca.h's limit on G D (D + 1) / 2
 PCA_KEYS = ("count", "mean", "cov", "eigenvalues", "components", "explained_variance_ratio", "projections", "sweeps", "off_norm")
 
 
 def infer_arguments(argv=None):
-    """infer.py's command line.  Everything after a bare `--` is kept aside (args.train_argv): with --generator/--inference
-    it is the training script's own flags, parsed later by that script's parser.  Refusals (exit code 2) are made here, before
-    anything touches a GPU or loads the kernel library."""
-    import argparse
-    argv = list(sys.argv[1:] if argv is None else argv)
-    train_argv = None
-    if "--" in argv:
-        cut = argv.index("--")
-        argv, train_argv = argv[:cut], argv[cut + 1:]
-    p = argparse.ArgumentParser("infer.py", description="Per-image pose, latents and K-sample importance-weighted likelihood "
-                                "of a trained spatial-VAE")
-    p.add_argument("script", choices=sorted(SCRIPTS), help="which training script made the model")
-    p.add_argument("--state", metavar="PATH.ckpt", help="training state file (--checkpoint_interval): model, arguments, dataset")
-    p.add_argument("--generator", metavar="G.sav", help="whole-module generator file; with --inference and, after `--`, the "
-                   "training script's own flags")
-    p.add_argument("--inference", metavar="Q.sav")
-    p.add_argument("--out", required=True, metavar="scores.npz")
-    p.add_argument("--split", choices=["test", "train"], default="test")
-    p.add_argument("--num_samples", type=int, default=64, metavar="K", help="samples per image (any K >= 1; default 64)")
-    p.add_argument("--chunk", type=int, default=64, metavar="C",
-                   help="samples per image decoded at once, 1..%d (default 64): memory is that of a B*C minibatch" % INFER_MAX_CHUNK)
-    p.add_argument("--minibatch_size", type=int, default=100, metavar="B")
-    p.add_argument("--seed", type=int, default=0, help="seed of the generator the N(0,1) draws come from")
-    p.add_argument("-d", "--device", type=int, default=-2)
-    for name in INFER_PATH_OVERRIDES:
-        p.add_argument("--" + name, default=None, help="instead of the path stored in the state file")
-    p.add_argument("--aligned", metavar="PATH", help="also write every image brought into the model's canonical frame (its "
-                   "pose removed), in dataset order: .npy = (images, rows, cols, C) float32, .mrcs = an MRC stack (one channel "
-                   "only).  The observed images resampled, nothing else: not masked, and CTF-corrected only under --ctf_correct flip")
-    p.add_argument("--recon", metavar="PATH", help="also write every image's pose-free reconstruction (the decoder on the "
-                   "un-posed grid at the image's content latents), same formats")
-    p.add_argument("--class_averages", metavar="PATH.npz", help="also write the sums, counts and averages of the aligned images "
-                   "over the pixels each image covers: per class of --labels, else one class of all images")
-    p.add_argument("--labels", metavar="PATH.npy", help="integer class per image of the split, -1 = in no class (with "
-                   "--class_averages; at most %d classes)" % INFER_MAX_CLASSES)
-    p.add_argument("--pose", choices=list(E.POSES), default=None, help="which estimate aligns, and whose content latents --recon "
-                   "decodes: the importance-weighted mean (iw, the default), the best sample, or q's mean")
-    p.add_argument("--interp", choices=["bicubic", "bilinear"], default=None, help="resampling of --aligned / --class_averages "
-                   "(default bicubic: Catmull-Rom)")
-    p.add_argument("--ctf_correct", choices=["flip", "wiener"], default=None, help="particles with a CTF table only: correct each "
-                   "observed image by its own transfer function H before it is aligned.  flip: multiply its Fourier coefficients "
-                   "by the sign of H; --aligned and the class averages then hold phase-flipped particles.  wiener: leave those as "
-                   "they are and add to --class_averages the Wiener averages sum(H y) / (sum(H^2) + lambda) per class, with their "
-                   "numerator and denominator.  Scoring is untouched either way")
-    p.add_argument("--wiener_lambda", type=float, default=None, metavar="X", help="with --ctf_correct wiener: the regulariser, "
-                   "X >= 0, the reciprocal of the per-particle spectral signal-to-noise ratio assumed (default 1.0: a convention, not "
-                   "a tuned value; the .npz keeps numerator and denominator, so another X needs no second run)")
-    p.add_argument("--cluster", type=int, default=None, metavar="K", help="k-means of the content latents into K classes on the "
-                   "device (2..%d, at most the number of images), seeded by k-means++; the classes take the place of --labels for "
-                   "--class_averages, and --pose selects whose content latents are clustered (z_iw, z_best or z_q)" % INFER_MAX_CLUSTERS)
-    p.add_argument("--cluster_out", metavar="PATH.npz", help="with --cluster (required): labels, centres, members, inertia, the "
-                   "seeds, every restart's inertia and the decoder's un-posed reconstruction of each centre")
-    p.add_argument("--cluster_labels", metavar="PATH.npy", help="with --cluster: also write the labels in the format --labels reads")
-    p.add_argument("--cluster_iters", type=int, default=None, metavar="I", help="Lloyd iterations per restart, I >= 1 (default 100; "
-                   "iterations after convergence change nothing)")
-    p.add_argument("--cluster_restarts", type=int, default=None, metavar="R", help="independent seedings, 1..%d (default 1); the one "
-                   "of lowest inertia is kept, the first of equals" % INFER_MAX_RESTARTS)
-    p.add_argument("--cluster_seed", type=int, default=None, metavar="S", help="seed of the generator the k-means++ uniforms come "
-                   "from (default --seed)")
-    p.add_argument("--cluster_gmm", type=int, default=None, metavar="I", help="with --cluster: fit a diagonal-covariance Gaussian "
-                   "mixture to the content latents by I EM iterations (1..%d) on the device, started from the k-means result.  Its "
-                   "labels take the place of the k-means labels for everything downstream; --cluster_out keeps the k-means arrays "
-                   "and gains the mixture's (gmm_*): responsibilities, log-likelihood, BIC and AIC among them" % INFER_MAX_GMM_ITERS)
-    p.add_argument("--cluster_gmm_reg", type=float, default=None, metavar="X", help="with --cluster_gmm: added to every variance, "
-                   "X > 0 (default 1e-6: a convention, not a tuned value)")
-    p.add_argument("--cluster_gmm_tol", type=float, default=None, metavar="X", help="with --cluster_gmm: the fit is frozen once an "
-                   "iteration gains no more than X |log-likelihood|, X >= 0 (default 1e-8, a convention too)")
-    p.add_argument("--cluster_min_resp", type=float, default=None, metavar="P", help="with --cluster_gmm: an image whose largest "
-                   "responsibility is below P, 0 <= P < 1, is in no class (label -1; default 0, a convention too: every image stays)")
-    p.add_argument("--pca", metavar="PATH.npz", help="also write the principal axes of the split's content latents (--pose selects "
-                   "whose: z_iw, z_best or z_q), found on the device: mean, covariance, eigenvalues, components (rows are axes), "
-                   "explained variance ratio and every image's projections")
-    p.add_argument("--pca_components", type=int, default=None, metavar="P", help="with --pca: the columns of projections, 1..z_dim "
-                   "(default z_dim)")
-    p.add_argument("--pca_traverse", type=int, default=None, metavar="Q", help="with --pca: also decode a walk along each of the first "
-                   "Q axes, 0..z_dim (default 0): traverse_latents and traverse_images")
-    p.add_argument("--pca_steps", type=int, default=None, metavar="T", help="with --pca_traverse: steps on each side of the mean, "
-                   "1..%d (default 5: 2 T + 1 frames)" % INFER_MAX_PCA_STEPS)
-    p.add_argument("--pca_span", type=float, default=None, metavar="X", help="with --pca_traverse: how far the walk reaches on each "
-                   "side, in standard deviations along the axis, a finite X > 0 (default 2.0)")
-    p.add_argument("--pca_per_class", action="store_true", help="with --pca and --cluster: also the principal axes of every class "
-                   "(the arrays prefixed class_), under the labels the class averages are built from; a walk starts from the "
-                   "class's mean along the class's own axes")
-    p.add_argument("--frc", action="store_true", help="with --class_averages: also accumulate each class over two disjoint halves "
-                   "(image i of the split in half i & 1) and add their sums, the Fourier ring correlation of the two half averages, "
-                   "the resolution at the 0.143 and 0.5 thresholds and the full average filtered by sqrt(2 FRC / (1 + FRC)).  One "
-                   "model aligns both halves, so the figure is optimistic")
-    p.add_argument("--frc_mask_radius", type=float, default=None, metavar="PX", help="with --frc: radius of the soft circular mask "
-                   "put on both half averages before the transform (default max(min(rows, cols)/2 - edge, 1): a convention, not a "
-                   "tuned value); 0 = no mask")
-    p.add_argument("--frc_mask_edge", type=float, default=None, metavar="PX", help="with --frc: width of the mask's raised-cosine "
-                   "edge, PX > 0 (default 3, a convention too)")
-    p.add_argument("--refine", type=int, default=None, metavar="R", help="with --class_averages: R rounds (1..%d) of reference-based "
-                   "alignment.  Each round takes the class averages as they stand as references, searches a small neighbourhood of "
-                   "rotations and shifts around every image's pose for the best weighted correlation with the average of its class, "
-                   "and accumulates the averages again at the new poses.  With --frc each half is refined against its own half "
-                   "average only.  The file keeps the first averages as average_unrefined" % INFER_MAX_REFINE_ROUNDS)
-    p.add_argument("--refine_angles", type=int, default=None, metavar="A", help="with --refine: rotations searched on each side of "
-                   "the current one, 0..%d (default 5)" % INFER_MAX_REFINE_ANGLES)
-    p.add_argument("--refine_step", type=float, default=None, metavar="DEG", help="with --refine: their spacing in degrees, DEG > 0 "
-                   "(default 2.0)")
-    p.add_argument("--refine_shift", type=int, default=None, metavar="S", help="with --refine: shifts searched, whole pixels up to S "
-                   "on both axes, 0..%d (default 2)" % INFER_MAX_REFINE_SHIFT)
-    p.add_argument("--reassign", action="store_true", help="with --refine: multi-reference alignment.  Each round scores every "
-                   "labelled image against the average of EVERY class over the same neighbourhood of poses and moves it to the class "
-                   "it fits best, then refines its pose against that class; with --frc against the averages of its own half only.  "
-                   "A class that loses every member has an all-zero average from then on, which the search skips: it stays empty")
-    p.add_argument("--reassign_labels", metavar="PATH.npy", help="with --reassign: also write the final labels in the format "
-                   "--labels reads")
-    p.add_argument("--refine_soft", action="store_true", help="with --refine --reassign: maximum-likelihood class averages.  Each "
-                   "round still names every image's best class and pose as --reassign does (labels, poses and --aligned keep their "
-                   "meaning), but the averages are accumulated softly: the image is spread over its best classes and over every "
-                   "rotation and shift of the search by its posterior probability under Gaussian noise, and added so weighted.  The "
-                   "class file's sum and count are then fractional")
-    p.add_argument("--refine_soft_classes", type=int, default=None, metavar="T", help="with --refine_soft: the classes an image is "
-                   "spread over, its T best of the round, 1..%d (default 8)" % INFER_MAX_SOFT_CLASSES)
-    p.add_argument("--refine_soft_sigma2", type=float, default=None, metavar="X", help="with --refine_soft: the noise variance per "
-                   "pixel, a finite X > 0 (default: estimated each round from the residuals of the images against the averages of "
-                   "their classes at their current poses)")
-    args = p.parse_args(argv)
-    args.train_argv = train_argv
-    if args.reassign and args.refine is None:
-        p.error("--reassign needs --refine")
-    if not args.refine_soft:
-        for name in ("refine_soft_classes", "refine_soft_sigma2"):
-            if vars(args)[name] is not None:
-                p.error("--%s needs --refine_soft" % name)
-    else:
-        if args.refine is None:
-            p.error("--refine_soft needs --refine")
-        if not args.reassign:
-            p.error("--refine_soft needs --reassign")
-        args.refine_soft_classes = 8 if args.refine_soft_classes is None else args.refine_soft_classes
-        if not 1 <= args.refine_soft_classes <= INFER_MAX_SOFT_CLASSES:
-            p.error("--refine_soft_classes must be in [1, %d] (got %d)" % (INFER_MAX_SOFT_CLASSES, args.refine_soft_classes))
-        if args.refine_soft_sigma2 is not None and not 0 < args.refine_soft_sigma2 < float("inf"):
-            p.error("--refine_soft_sigma2 must be a finite number > 0 (got %r)" % args.refine_soft_sigma2)
-    if args.reassign_labels is not None:
-        if not args.reassign:
-            p.error("--reassign_labels needs --reassign")
-        if os.path.splitext(args.reassign_labels)[1] != ".npy":
-            p.error("--reassign_labels must end in .npy (got %s)" % args.reassign_labels)
-    if args.refine is None:
-        for name in ("refine_angles", "refine_step", "refine_shift"):
-            if vars(args)[name] is not None:
-                p.error("--%s needs --refine" % name)
-    else:
-        if not 1 <= args.refine <= INFER_MAX_REFINE_ROUNDS:
-            p.error("--refine must be in [1, %d] (got %d)" % (INFER_MAX_REFINE_ROUNDS, args.refine))
-        if args.class_averages is None:
-            p.error("--refine needs --class_averages")
-        if args.ctf_correct == "wiener":
-            p.error("--refine does not take --ctf_correct wiener: the half references would need half denominators")
-        args.refine_angles = 5 if args.refine_angles is None else args.refine_angles
-        args.refine_step = 2.0 if args.refine_step is None else args.refine_step
-        args.refine_shift = 2 if args.refine_shift is None else args.refine_shift
-        if not 0 <= args.refine_angles <= INFER_MAX_REFINE_ANGLES:
-            p.error("--refine_angles must be in [0, %d] (got %d)" % (INFER_MAX_REFINE_ANGLES, args.refine_angles))
-        if not 0 < args.refine_step < float("inf"):
-            p.error("--refine_step must be a finite number > 0 (got %r)" % args.refine_step)
-        if not 0 <= args.refine_shift <= INFER_MAX_REFINE_SHIFT:
-            p.error("--refine_shift must be in [0, %d] (got %d)" % (INFER_MAX_REFINE_SHIFT, args.refine_shift))
-    if not args.frc:
-        for name in ("frc_mask_radius", "frc_mask_edge"):
-            if vars(args)[name] is not None:
-                p.error("--%s needs --frc" % name)
-    else:
-        if args.class_averages is None:
-            p.error("--frc needs --class_averages")
-        if args.frc_mask_radius is not None and not 0 <= args.frc_mask_radius < float("inf"):
-            p.error("--frc_mask_radius must be a finite number >= 0 (got %r)" % args.frc_mask_radius)
-        args.frc_mask_edge = 3.0 if args.frc_mask_edge is None else args.frc_mask_edge
-        if not 0 < args.frc_mask_edge < float("inf"):
-            p.error("--frc_mask_edge must be a finite number > 0 (got %r)" % args.frc_mask_edge)
-    if args.cluster is None:
-        for name in ("cluster_out", "cluster_labels", "cluster_iters", "cluster_restarts", "cluster_seed"):
-            if vars(args)[name] is not None:
-                p.error("--%s needs --cluster" % name)
-    else:
-        if not 2 <= args.cluster <= INFER_MAX_CLUSTERS:
-            p.error("--cluster must be in [2, %d] (got %d)" % (INFER_MAX_CLUSTERS, args.cluster))
-        if args.labels is not None:
-            p.error("--cluster makes the classes itself: it excludes --labels")
-        if args.cluster_out is None:
-            p.error("--cluster needs --cluster_out")
-        if os.path.splitext(args.cluster_out)[1] != ".npz":
-            p.error("--cluster_out must end in .npz (got %s)" % args.cluster_out)
-        if args.cluster_labels is not None and os.path.splitext(args.cluster_labels)[1] != ".npy":
-            p.error("--cluster_labels must end in .npy (got %s)" % args.cluster_labels)
-        args.cluster_iters = 100 if args.cluster_iters is None else args.cluster_iters
-        args.cluster_restarts = 1 if args.cluster_restarts is None else args.cluster_restarts
-        args.cluster_seed = args.seed if args.cluster_seed is None else args.cluster_seed
-        if args.cluster_iters < 1:
-            p.error("--cluster_iters must be >= 1")
-        if not 1 <= args.cluster_restarts <= INFER_MAX_RESTARTS:
-            p.error("--cluster_restarts must be in [1, %d]" % INFER_MAX_RESTARTS)
-    if args.cluster_gmm is None:
-        for name in ("cluster_gmm_reg", "cluster_gmm_tol", "cluster_min_resp"):
-            if vars(args)[name] is not None:
-                p.error("--%s needs --cluster_gmm" % name)
-    else:
-        if args.cluster is None:
-            p.error("--cluster_gmm needs --cluster")
-        if not 1 <= args.cluster_gmm <= INFER_MAX_GMM_ITERS:
-            p.error("--cluster_gmm must be in [1, %d] (got %d)" % (INFER_MAX_GMM_ITERS, args.cluster_gmm))
-        args.cluster_gmm_reg = 1e-6 if args.cluster_gmm_reg is None else args.cluster_gmm_reg
-        args.cluster_gmm_tol = 1e-8 if args.cluster_gmm_tol is None else args.cluster_gmm_tol
-        args.cluster_min_resp = 0.0 if args.cluster_min_resp is None else args.cluster_min_resp
-        if not 0 < args.cluster_gmm_reg < float("inf"):
-            p.error("--cluster_gmm_reg must be a finite number > 0 (got %r)" % args.cluster_gmm_reg)
-        if not 0 <= args.cluster_gmm_tol < float("inf"):
-            p.error("--cluster_gmm_tol must be a finite number >= 0 (got %r)" % args.cluster_gmm_tol)
-        if not 0 <= args.cluster_min_resp < 1:
-            p.error("--cluster_min_resp must be in [0, 1) (got %r)" % args.cluster_min_resp)
-    if args.pca is None:
-        for name in ("pca_components", "pca_traverse", "pca_steps", "pca_span"):
-            if vars(args)[name] is not None:
-                p.error("--%s needs --pca" % name)
-        if args.pca_per_class:
-            p.error("--pca_per_class needs --pca")
-    else:
-        if os.path.splitext(args.pca)[1] != ".npz":
-            p.error("--pca must end in .npz (got %s)" % args.pca)
-        if args.pca_per_class and args.cluster is None:
-            p.error("--pca_per_class needs --cluster")
-        args.pca_traverse = 0 if args.pca_traverse is None else args.pca_traverse
-        args.pca_steps = 5 if args.pca_steps is None else args.pca_steps
-        args.pca_span = 2.0 if args.pca_span is None else args.pca_span
-        if args.pca_components is not None and args.pca_components < 1:
-            p.error("--pca_components must be >= 1 (got %d)" % args.pca_components)
-        if args.pca_traverse < 0:
-            p.error("--pca_traverse must be >= 0 (got %d)" % args.pca_traverse)
-        if not 1 <= args.pca_steps <= INFER_MAX_PCA_STEPS:
-            p.error("--pca_steps must be in [1, %d] (got %d)" % (INFER_MAX_PCA_STEPS, args.pca_steps))
-        if not 0 < args.pca_span < float("inf"):
-            p.error("--pca_span must be a finite number > 0 (got %r)" % args.pca_span)
-    if args.ctf_correct is not None and args.script != "particles":
-        p.error("--ctf_correct is for particles (the script whose images have a CTF), not %s" % args.script)
-    if args.ctf_correct == "flip" and args.aligned is None and args.class_averages is None:
-        p.error("--ctf_correct flip needs one of --aligned, --class_averages")
-    if args.ctf_correct == "wiener" and args.class_averages is None:
-        p.error("--ctf_correct wiener needs --class_averages")
-    if args.wiener_lambda is not None:
-        if args.ctf_correct != "wiener":
-            p.error("--wiener_lambda needs --ctf_correct wiener")
-        if not 0 <= args.wiener_lambda < float("inf"):
-            p.error("--wiener_lambda must be a finite number >= 0 (got %r)" % args.wiener_lambda)
-    elif args.ctf_correct == "wiener":
-        args.wiener_lambda = 1.0
-    if args.num_samples < 1:
-        p.error("--num_samples must be >= 1")
-    if not 1 <= args.chunk <= INFER_MAX_CHUNK:
-        p.error("--chunk must be in [1, %d]" % INFER_MAX_CHUNK)
-    if args.minibatch_size < 1:
-        p.error("--minibatch_size must be >= 1")
-    sav = args.generator is not None or args.inference is not None
-    if (args.state is None) == (not sav):
-        p.error("give either --state or --generator with --inference")
-    if sav and (args.generator is None or args.inference is None):
-        p.error("--generator and --inference go together")
-    if sav and train_argv is None:
-        p.error("--generator/--inference need the training script's flags after `--`")
-    if not sav and train_argv:
-        p.error("--state carries the training arguments: nothing may follow `--`")
-    for path in (args.state, args.generator, args.inference):
-        if path is not None and not os.path.isfile(path):
-            p.error("no such file: %s" % path)
-    for name in ("aligned", "recon"):
-        path = vars(args)[name]
-        if path is not None and os.path.splitext(path)[1] not in INFER_STACK_FORMATS:
-            p.error("--%s must end in .npy or .mrcs (got %s)" % (name, path))
-    if args.class_averages is not None and os.path.splitext(args.class_averages)[1] != ".npz":
-        p.error("--class_averages must end in .npz (got %s)" % args.class_averages)
-    if args.labels is not None and args.class_averages is None:
-        p.error("--labels needs --class_averages")
-    if args.aligned is None and args.recon is None and args.class_averages is None:
-        for name in ("pose", "interp"):
-            if vars(args)[name] is not None and not (name == "pose" and (args.cluster is not None or args.pca is not None)):
-                p.error("--%s needs one of --aligned, --recon, --class_averages" % name)
-    args.pose, args.interp = args.pose or "iw", args.interp or "bicubic"
-    args.label_array = None
-    if args.labels is not None:
-        try:
-            args.label_array = read_labels(args.labels)
-        except ValueError as e:
-            p.error(str(e))
-        if args.frc and args.label_array.size and args.label_array.max() + 1 > INFER_FRC_MAX_CLASSES:
-            p.error("--frc keeps two sums per class: at most %d classes (--labels has %d)"
-                    % (INFER_FRC_MAX_CLASSES, args.label_array.max() + 1))
-    classes = args.cluster if args.cluster is not None else 1 if args.label_array is None or not args.label_array.size \
-        else int(args.label_array.max()) + 1
-    if args.reassign and classes > INFER_MAX_REASSIGN_CLASSES:
-        p.error("--reassign scores every image against every class: at most %d classes (got %d)" % (INFER_MAX_REASSIGN_CLASSES, classes))
-    return args
-
-
-def frc_mask_radius(args, n, m):
-    """--frc_mask_radius, or its default for an n x m box: max(min(n, m)/2 - edge, 1)."""
-    return max(min(n, m) / 2.0 - args.frc_mask_edge, 1.0) if args.frc_mask_radius is None else float(args.frc_mask_radius)
-
-
-def read_labels(path):
-    """The int64 class labels of a --labels file; ValueError with the reason when it is no 1-D integer .npy with values >= -1
-    and at most INFER_MAX_CLASSES classes."""
-    if not os.path.isfile(path):
-        raise ValueError("no such file: %s" % path)
-    try:
-        labels = np.load(path, allow_pickle=False)
-    except Exception as e:
-        raise ValueError("--labels %s is not a .npy array: %s" % (path, e))
-    if not isinstance(labels, np.ndarray) or labels.dtype.kind not in "iu":
-        raise ValueError("--labels %s must be an integer array (got %s)" % (path, getattr(labels, "dtype", type(labels).__name__)))
-    if labels.ndim != 1:
-        raise ValueError("--labels %s must be 1-D, one entry per image (got shape %s)" % (path, labels.shape))
-    labels = labels.astype(np.int64)
-    if labels.size and labels.min() < -1:
-        raise ValueError("--labels %s has a value below -1 (%d)" % (path, labels.min()))
-    if labels.size and labels.max() + 1 > INFER_MAX_CLASSES:
-        raise ValueError("--labels %s has %d classes, at most %d are supported" % (path, labels.max() + 1, INFER_MAX_CLASSES))
-    return labels
-
-
-def _refuse(message):
-    print("infer.py: " + message, file=sys.stderr)
-    raise SystemExit(2)
+    """infer_request.infer_arguments, under this module's INFER_MAX_REASSIGN_CLASSES: the one limit that no command line can
+    reach (--labels and --cluster stop below it) and that is therefore seen only when lowered here."""
+    return infer_request.infer_arguments(argv, INFER_MAX_REASSIGN_CLASSES)
 
 
 def stored_namespace(ck, defaults, script):
@@ -491,69 +157,12 @@ def load_model(args, parser_fn, build, positional):
     return Model(targs, cfg, p_net.to(device).eval(), q_net.to(device).eval(), z_scale, device, completed)
 
 
-# What check_request needs to know of the split and the model, as plain Python values.  ctf_rows: the rows of the split's CTF
-# parameter table, None = it has none.
-SplitFacts = collections.namedtuple("SplitFacts", "images n m channels rotate translate inf_dim z_scale split ctf_rows")
-
-
 def split_facts(args, model):
     cfg = model.cfg
     data, n, m = cfg["y_" + args.split], cfg["n"], cfg["m"]
     table = cfg.get("ctf_params_" + args.split)
     return SplitFacts(data.size(0), n, m, data[0].numel() // (n * m) if data.size(0) else 1, cfg["rotate"], cfg["translate"],
                       model.q_net.latent_dim, model.z_scale, args.split, None if table is None else table.shape[0])
-
-
-def check_request(args, facts):
-    """Every refusal (exit code 2) that depends on the data or the model: a function of the arguments and the facts alone, made
-    before anything is allocated for the run."""
-    images, channels = facts.images, facts.channels
-    if args.cluster is not None:
-        if E.row_layout(facts.rotate, facts.translate, facts.inf_dim).z_dim < 1:
-            _refuse("--cluster groups the content latents, and this model has none (z_dim = 0)")
-        if facts.z_scale == 0:
-            _refuse("--cluster: this state is from before the run's z_delay ended (z_scale = 0): every content latent is 0")
-        if args.cluster > images:
-            _refuse("--cluster {} exceeds the {} images of the {} split".format(args.cluster, images, facts.split))
-        if args.cluster_gmm is not None and images * args.cluster > INFER_MAX_GMM_RESP:
-            _refuse("--cluster_gmm keeps a responsibility per image and class: {} images x {} classes exceed 2^28".format(
-                images, args.cluster))
-    if args.pca is not None:
-        z_dim = E.row_layout(facts.rotate, facts.translate, facts.inf_dim).z_dim
-        if z_dim < 1:
-            _refuse("--pca takes the axes of the content latents, and this model has none (z_dim = 0)")
-        if images < 1:
-            _refuse("--pca: the {} split has no image".format(facts.split))
-        if args.pca_components is not None and args.pca_components > z_dim:
-            _refuse("--pca_components must be in [1, {0}], this model's z_dim (got {1})".format(z_dim, args.pca_components))
-        if args.pca_traverse > z_dim:
-            _refuse("--pca_traverse must be in [0, {0}], this model's z_dim (got {1})".format(z_dim, args.pca_traverse))
-        if args.pca_per_class and args.cluster * (z_dim * (z_dim + 1) // 2) > INFER_MAX_PCA_PARTIALS:
-            _refuse("--pca_per_class keeps z_dim (z_dim + 1) / 2 products per class: {} classes x {} exceed {}".format(
-                args.cluster, z_dim * (z_dim + 1) // 2, INFER_MAX_PCA_PARTIALS))
-    if args.refine is not None:
-        if not facts.rotate and not facts.translate:
-            _refuse("--refine searches rotations and shifts, and this model infers neither")
-        if max(facts.n, facts.m) > INFER_FRC_MAX_BOX:
-            _refuse("--refine takes boxes of at most {0}x{0} pixels, these images are {1}x{2}".format(INFER_FRC_MAX_BOX, facts.n, facts.m))
-    if args.frc and max(facts.n, facts.m) > INFER_FRC_MAX_BOX:
-        _refuse("--frc takes boxes of at most {0}x{0} pixels, these images are {1}x{2}".format(INFER_FRC_MAX_BOX, facts.n, facts.m))
-    if args.label_array is not None and args.label_array.shape[0] != images:
-        _refuse("--labels has {} entries, the {} split has {} images".format(args.label_array.shape[0], facts.split, images))
-    for k in ("aligned", "recon"):
-        path = vars(args)[k]
-        if path is not None and path.endswith(".mrcs") and channels != 1:
-            _refuse("--{} {}: an MRC stack holds one channel, these images have {}".format(k, path, channels))
-    if args.ctf_correct is not None:
-        if facts.ctf_rows is None:
-            _refuse("--ctf_correct needs the CTF parameters of the {0} split: the run has no --ctf-{0} table".format(facts.split))
-        if facts.ctf_rows < images:
-            _refuse("the CTF table of the {} split has {} rows, the split has {} images".format(facts.split, facts.ctf_rows, images))
-        if channels != 1:
-            _refuse("--ctf_correct takes one-channel images, these have {}".format(channels))
-        if facts.rotate and facts.n != facts.m:
-            _refuse("--ctf_correct on a model that rotates needs a square box (the transfer function commutes with the rotation "
-                    "only there); these images are {}x{}".format(facts.n, facts.m))
 
 
 Split = collections.namedtuple("Split", "data ctf mask x")
@@ -935,35 +544,21 @@ def collect(args, facts, lay, rows, acc, fit, centres, axes=None):
         torch.cuda.synchronize(acc.device)          # every minibatch's copy has landed
     arrays = score_arrays(*split_rows(host, lay), facts.rotate, facts.translate)
     means = [float(np.mean(arrays[k], dtype=np.float64)) for k in ("bound", "loglik", "kl")]
-    meta = {"script": args.script, "state": args.state, "generator": args.generator, "inference": args.inference,
-            "num_samples": args.num_samples, "chunk": args.chunk, "seed": args.seed, "split": args.split,
-            "images": int(host.shape[0]), "mean_bound": means[0], "mean_loglik": means[1], "mean_kl": means[2]}
-    want = {k: vars(args)[k] for k in ("aligned", "recon", "class_averages")}
-    if any(v is not None for v in want.values()):   # only then: without the options the file is what it always was
-        meta.update(pose=args.pose, interp=args.interp, labels=args.labels, **want)
-    if args.ctf_correct is not None:
-        meta.update(ctf_correct=args.ctf_correct, wiener_lambda=args.wiener_lambda)
-    if args.frc:
-        meta.update(frc=True, frc_mask_radius=frc_mask_radius(args, facts.n, facts.m), frc_mask_edge=args.frc_mask_edge)
+    figures = {"images": int(host.shape[0]), "mean_bound": means[0], "mean_loglik": means[1], "mean_kl": means[2]}
     if acc.refined is not None:
-        meta.update(refine=args.refine, refine_angles=args.refine_angles, refine_step=args.refine_step, refine_shift=args.refine_shift)
         arrays.update(pose_refined=acc.refined["pose"].cpu().numpy(), refine_score=acc.refined["score"].cpu().numpy(),
                       refine_offset=acc.refined["offset"].cpu().numpy())
         if args.reassign:
-            meta.update(reassign=True, reassign_labels=args.reassign_labels)
             arrays.update(label_refined=acc.refined["label"].cpu().numpy().astype(np.int64),
                           refine_label=acc.refined["labels"].cpu().numpy(), refine_moved=acc.refined["moved"].cpu().numpy(),
                           refine_class_score=acc.refined["class_score"].cpu().numpy(),
                           refine_class_margin=acc.refined["margin"].cpu().numpy())
         if args.refine_soft:
             soft = acc.refined["soft"]
-            meta.update(refine_soft=True, refine_soft_classes=args.refine_soft_classes, refine_soft_sigma2=args.refine_soft_sigma2)
             arrays.update(refine_soft_sigma2=soft["sigma2"].numpy(), refine_log_evidence=soft["log_evidence"].cpu().numpy(),
                           refine_post_max=soft["post_max"].cpu().numpy(), refine_class_post=soft["class_post"].cpu().numpy())
     found, labels = None, acc.labels
     if fit is not None:
-        meta.update(pose=args.pose, cluster=args.cluster, cluster_out=args.cluster_out, cluster_labels=args.cluster_labels,
-                    cluster_iters=args.cluster_iters, cluster_restarts=args.cluster_restarts, cluster_seed=args.cluster_seed)
         labels = fit["label"].cpu().numpy().astype(np.int64)
         record = ops.KMeans.read_record(fit["record"])
         found = {"label": labels, "centres": fit["centres"].cpu().numpy(), "members": fit["members"].cpu().numpy(),
@@ -972,16 +567,11 @@ def collect(args, facts, lay, rows, acc, fit, centres, axes=None):
                  "restart_inertia": fit["restart_inertia"].cpu().numpy(), "chosen_restart": np.int64(fit["chosen_restart"].item()),
                  "centre_recon": centres.cpu().numpy().reshape(args.cluster, facts.n, facts.m, -1)}
         if args.cluster_gmm is not None:
-            meta.update(cluster_gmm=args.cluster_gmm, cluster_gmm_reg=args.cluster_gmm_reg, cluster_gmm_tol=args.cluster_gmm_tol,
-                        cluster_min_resp=args.cluster_min_resp)
             found.update(mixture_arrays(args, facts, fit))
             labels = found["gmm_label_used"]
-        found["meta"] = np.array(json.dumps(meta))
-    pca = None
-    if axes is not None:                            # after the cluster file's meta: that file stays what it was
-        meta.update(pca=args.pca, pca_pose=args.pose, pca_components=args.pca_components, pca_traverse=args.pca_traverse,
-                    pca_steps=args.pca_steps, pca_span=args.pca_span, pca_per_class=args.pca_per_class)
-        pca = pca_arrays(args, facts, axes, meta)
+        found["meta"] = np.array(json.dumps(run_meta(args, facts, figures, without=("pca",))))  # that file stays what it was
+    meta = run_meta(args, facts, figures)
+    pca = pca_arrays(args, facts, axes, meta) if axes is not None else None
     arrays["meta"] = np.array(json.dumps(meta))
     summary = "images {}\tbound {!r}\tlog p(x|z) {!r}\tKL {!r}\tmedian ESS {:.3f}".format(
         host.shape[0], means[0], means[1], means[2], float(np.median(arrays["ess"])))

@@ -967,12 +967,14 @@ class KMeans:
     same bits; nothing is read back.  A point with a non-finite coordinate gets the label -1 and enters nothing."""
 
     RECORD_WORDS = ctypes.sizeof(_lib.KMeansRecord) // 8
+    MAX_K = 1024                # include/svae_cluster.h's limits on k and D
+    MAX_D = 64
 
     def __init__(self, k, D, device):
         device = _hip_device("KMeans", device)
         self.k, self.D, self.device = int(k), int(D), device
-        if not (1 <= self.k <= 1024 and 1 <= self.D <= 64):
-            raise RuntimeError("KMeans: k = %d must be in 1..1024 and D = %d in 1..64" % (self.k, self.D))
+        if not (1 <= self.k <= self.MAX_K and 1 <= self.D <= self.MAX_D):
+            raise RuntimeError("KMeans: k = %d must be in 1..%d and D = %d in 1..%d" % (self.k, self.MAX_K, self.D, self.MAX_D))
 
     def fit(self, points, iters, uniforms):
         """Seed, `iters` update steps and one final assign-only step, all enqueued on the current stream.  points: (N, D) fp32
@@ -1022,12 +1024,14 @@ class GaussianMixture:
     nothing is read back.  A point with a non-finite coordinate gets the label -1 and an all-zero row of responsibilities."""
 
     RECORD_WORDS = ctypes.sizeof(_lib.GmmRecord) // 8
+    MAX_K = 1024                # include/svae_gmm.h's limits on k and D
+    MAX_D = 64
 
     def __init__(self, k, D, device):
         device = _hip_device("GaussianMixture", device)
         self.k, self.D, self.device = int(k), int(D), device
-        if not (1 <= self.k <= 1024 and 1 <= self.D <= 64):
-            raise RuntimeError("GaussianMixture: k = %d must be in 1..1024 and D = %d in 1..64" % (self.k, self.D))
+        if not (1 <= self.k <= self.MAX_K and 1 <= self.D <= self.MAX_D):
+            raise RuntimeError("GaussianMixture: k = %d must be in 1..%d and D = %d in 1..%d" % (self.k, self.MAX_K, self.D, self.MAX_D))
 
     def fit(self, points, label, centres, iters, reg=1e-6, tol=1e-8):
         """svae_gmm_init from the k-means `label` (N) int32 and `centres` (k, D) float64, `iters` update steps and one labelling

@@ -161,3 +161,124 @@ def test_stream_binding_matches_its_header():
         fn = getattr(L, name)
         assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
     assert L.svae_abi_version() == 2
+
+
+def _snapshot_files(snapshot, tmp_path):
+    for name in ("a.ckpt", "g.sav", "q.sav"):
+        (tmp_path / name).write_bytes(b"x")
+    for name, spec in snapshot["label_files"].items():
+        np.save(str(tmp_path / name), np.array(spec["data"], dtype=spec["dtype"]))
+
+
+def test_command_line_reproduces_the_snapshot_taken_before_the_options_became_a_table(tmp_path, capsys, monkeypatch):
+    """tests/golden/infer_args_snapshot.json (gen_infer_args_snapshot.py, run at the commit the file names, where
+    infer_arguments and check_request were ladders of refusals): the --help text; for every accepted argv the ordered (key, value)
+    pairs of vars(args) with their types; for every refused argv -- one at least for each p.error call of that commit, and those
+    that break two rules at once -- exit code 2, the usage and the exact last line of stderr; for every (argv, SplitFacts) pair
+    -- one at least for each _refuse call of that commit's check_request -- the exact refusal, or none.  {tmp} in an argv or a
+    message is the directory holding the files that must exist."""
+    infer = _infer()
+    with open(os.path.join(ROOT, "tests", "golden", "infer_args_snapshot.json")) as f:
+        snapshot = json.load(f)
+    assert len(snapshot["p_error_lines"]) == 61 and len(snapshot["refuse_lines"]) == 18
+    _snapshot_files(snapshot, tmp_path)
+    monkeypatch.setenv("COLUMNS", snapshot["columns"])
+
+    def there(text):
+        return text.replace("{tmp}", str(tmp_path))
+
+    with pytest.raises(SystemExit) as e:
+        infer.infer_arguments(["--help"])
+    assert e.value.code == 0 and " ".join(capsys.readouterr().out.split()) == snapshot["help"]
+    for c in snapshot["accepted"]:
+        args = infer.infer_arguments([there(a) for a in c["argv"]])
+        got = [[k, v.tolist() if isinstance(v, np.ndarray) else v] for k, v in vars(args).items()]
+        want = [[k, there(v) if isinstance(v, str) else v] for k, v in zip(snapshot["keys"], c["values"])]
+        assert got == want, c["argv"]
+        assert [type(v) for _, v in got] == [type(v) for _, v in want], c["argv"]     # 2 is not 2.0 here
+        assert args.label_array is None or args.label_array.dtype == np.int64
+    assert len(snapshot["refused"]) >= 61 + 10
+    for c in snapshot["refused"]:
+        with monkeypatch.context() as lowered:
+            for k, v in c.get("lowered", {}).items():
+                lowered.setattr(infer, k, v)
+            with pytest.raises(SystemExit) as e:
+                infer.infer_arguments([there(a) for a in c["argv"]])
+        usage, message = capsys.readouterr().err.rstrip("\n").rsplit("\n", 1)
+        assert e.value.code == 2 and message == there(c["error"]), c["argv"]
+        assert " ".join(usage.split()) == snapshot["usage"], c["argv"]
+    for c in snapshot["requests"]:
+        args = infer.infer_arguments([there(a) for a in c["argv"]])
+        capsys.readouterr()
+        if c["error"] is None:
+            assert infer.check_request(args, infer.SplitFacts(**c["facts"])) is None, (c["argv"], c["facts"])
+            assert capsys.readouterr().err == ""
+            continue
+        with pytest.raises(SystemExit) as e:
+            infer.check_request(args, infer.SplitFacts(**c["facts"]))
+        assert e.value.code == 2 and capsys.readouterr().err == there(c["error"]) + "\n", (c["argv"], c["facts"])
+
+
+BASE_META = ["script", "state", "generator", "inference", "num_samples", "chunk", "seed", "split", "images", "mean_bound",
+             "mean_loglik", "mean_kl"]
+OUTPUT_META = ["pose", "interp", "labels", "aligned", "recon", "class_averages"]
+FRC_META = ["frc", "frc_mask_radius", "frc_mask_edge"]
+REFINE_META = ["refine", "refine_angles", "refine_step", "refine_shift"]
+CLUSTER_META = ["cluster", "cluster_out", "cluster_labels", "cluster_iters", "cluster_restarts", "cluster_seed"]
+GMM_META = ["cluster_gmm", "cluster_gmm_reg", "cluster_gmm_tol", "cluster_min_resp"]
+PCA_META = ["pca", "pca_pose", "pca_components", "pca_traverse", "pca_steps", "pca_span", "pca_per_class"]
+C_NPZ = ["--class_averages", "c.npz"]
+K_NPZ = ["--cluster", "3", "--cluster_out", "k.npz"]
+
+
+@pytest.mark.parametrize("script,extra,keys", [
+    ("mnist", [], []),
+    ("mnist", ["--pca", "p.npz", "--pose", "best"], PCA_META),
+    ("mnist", ["--aligned", "a.npy"], OUTPUT_META),
+    ("mnist", ["--recon", "r.npy", "--pose", "q"], OUTPUT_META),
+    ("mnist", C_NPZ + ["--labels", "{labels}"], OUTPUT_META),
+    ("particles", C_NPZ + ["--ctf_correct", "wiener"], OUTPUT_META + ["ctf_correct", "wiener_lambda"]),
+    ("particles", ["--aligned", "a.npy", "--ctf_correct", "flip"], OUTPUT_META + ["ctf_correct", "wiener_lambda"]),
+    ("mnist", C_NPZ + ["--frc"], OUTPUT_META + FRC_META),
+    ("mnist", C_NPZ + ["--frc", "--frc_mask_radius", "0"], OUTPUT_META + FRC_META),
+    ("mnist", C_NPZ + ["--refine", "2"], OUTPUT_META + REFINE_META),
+    ("mnist", C_NPZ + ["--refine", "2", "--reassign"], OUTPUT_META + REFINE_META + ["reassign", "reassign_labels"]),
+    ("mnist", C_NPZ + ["--refine", "2", "--reassign", "--refine_soft", "--frc"],
+     OUTPUT_META + FRC_META + REFINE_META + ["reassign", "reassign_labels", "refine_soft", "refine_soft_classes", "refine_soft_sigma2"]),
+    ("mnist", K_NPZ, ["pose"] + CLUSTER_META),
+    ("mnist", K_NPZ + C_NPZ, OUTPUT_META + CLUSTER_META),
+    ("mnist", K_NPZ + ["--cluster_gmm", "4"], ["pose"] + CLUSTER_META + GMM_META),
+    ("mnist", K_NPZ + ["--pca", "p.npz", "--pca_per_class", "--pca_traverse", "1"], ["pose"] + CLUSTER_META + PCA_META),
+    ("particles", K_NPZ + C_NPZ + ["--cluster_gmm", "4", "--ctf_correct", "flip", "--frc", "--refine", "1", "--reassign", "--pca", "p.npz"],
+     OUTPUT_META + ["ctf_correct", "wiener_lambda"] + FRC_META + REFINE_META + ["reassign", "reassign_labels"] + CLUSTER_META + GMM_META
+     + PCA_META),
+])
+def test_meta_is_made_from_the_groups_in_one_order(tmp_path, script, extra, keys):
+    """run_meta without a device: after the twelve keys every file has, the keys of each active group, in the one order
+    json.dumps will write.  pose, interp and labels only with an image output; pose again under --cluster, where it keeps its
+    first place; the pose --pca used as pca_pose; frc_mask_radius as computed for the box; every value the argument's own, with
+    its type; and the --cluster_out file's meta (without="pca") is the same record cut off before the pca_* keys."""
+    infer = _infer()
+    state, labels = tmp_path / "a.ckpt", tmp_path / "l.npy"
+    state.write_bytes(b"x")
+    np.save(str(labels), np.array([0, 1, -1, 1]))
+    args = infer.infer_arguments([script, "--state", str(state), "--out", "s.npz", "--seed", "7"] + [a.format(labels=labels) for a in extra])
+    facts = infer.SplitFacts(images=4, n=12, m=10, channels=1, rotate=True, translate=True, inf_dim=5, z_scale=1, split="test",
+                             ctf_rows=4)
+    figures = {"images": 4, "mean_bound": -1.5, "mean_loglik": -1.0, "mean_kl": 0.5}
+    meta = infer.run_meta(args, facts, figures)
+    assert list(meta) == BASE_META + keys
+    assert [meta[k] for k in BASE_META] == [script, str(state), None, None, 64, 64, 7, "test", 4, -1.5, -1.0, 0.5]
+    computed = {"pca_pose": args.pose, "frc_mask_radius": infer.frc_mask_radius(args, 12, 10) if args.frc else None}
+    for k in keys:
+        want = computed.get(k, vars(args).get(k))
+        assert meta[k] == want and type(meta[k]) is type(want), k
+    if "frc" in keys:
+        assert meta["frc_mask_radius"] == (0.0 if "--frc_mask_radius" in extra else 2.0) and meta["frc"] is True
+    if "cluster" in keys:
+        assert meta["cluster_seed"] == 7 and meta["pose"] == "iw"
+    if "--labels" in extra:
+        assert meta["labels"] == str(labels) and "label_array" not in meta
+    cut = infer.run_meta(args, facts, figures, without=("pca",))
+    assert list(cut.items()) == [(k, v) for k, v in meta.items() if not k.startswith("pca")]
+    assert json.loads(json.dumps(meta)) == meta and list(json.loads(json.dumps(meta))) == list(meta)
