@@ -281,12 +281,18 @@ int svae_colsum(const float* x, int32_t rows, int32_t cols, float* out, svae_str
 /*
  * A Linear layer of the inference network with its activation, for the small row counts of the encoder (one row per image):
  * replaces nn.Linear + activation() of InferenceNetwork.layers (spatial_vae/models.py:31-43, 46-54) and their autograd
- * backward.  fp32 MFMA (v_mfma_f32_16x16x4_f32), one 16 x 16 output tile per wave, bias and activation in the epilogue.
+ * backward.  fp32 MFMA (v_mfma_f32_16x16x4_f32), one 16 x 16 output tile per workgroup of four waves (each contracts a quarter,
+ * summed in a fixed order), bias and activation in the epilogue.
  *   forward : out[m][n] = act( sum_k x[m][k] weight[n][k] + bias[n] );  x (rows, in), weight (out, in) as nn.Linear keeps it,
  *             bias (out) or NULL, out (rows, out);  act = SVAE_ACT_* or SVAE_LINEAR_ACT_NONE
  *   backward: with dpre = dout * act'(out):  dweight (out, in) = dpre^T x,  dbias (out) = column sums of dpre,
  *             dx (rows, in) = dpre weight -- any of the three may be NULL; ONE launch produces all that are asked for.
  *             `out` is the forward's output (act' is taken through it); it may be NULL when act == SVAE_LINEAR_ACT_NONE.
+ * Alignment: any 4-byte-aligned pointers are accepted.  The kernels that read 16 bytes at a time along the contracted dimension
+ * run when that dimension is a multiple of 4 AND the operands read along it are 16-byte aligned -- in_features with x and
+ * weight for the forward, out_features with dout and out for dx -- and scalar-load kernels otherwise.  The two kinds sum the
+ * contraction in different orders, so an aligned and an unaligned call on the same values may differ in the last bits; each
+ * is reproducible by itself.
  * Meant for layers whose weights are a few MB; the first layer of the galaxy encoder (49 152 x 5 000) is a real GEMM and
  * stays with the vendor library.
  */
@@ -372,7 +378,9 @@ int svae_adam_step_guarded(float* param, float* grad, float* exp_avg, float* exp
  *   matrix    (B, 6) doubles ON THE DEVICE: the inverse affine coefficients Image.rotate derives from the angle
  *             (cos/sin of -radians(angle) rounded to 15 decimals, centre (cols/2, rows/2)); ignored where quarter >= 0.
  *   quarter   (B) int32 on the device: -1 = use the matrix; 0..3 = exact counter-clockwise quarter turns (Pillow's
- *             fast paths for angle % 360 in {0, 90, 180, 270}).
+ *             fast paths for angle % 360 in {0, 90, 180, 270}).  Codes 1 and 3 REQUIRE rows == cols (Pillow takes those fast
+ *             paths for square images only; on any other image the transposed index leaves the buffer): for a non-square
+ *             image send -1 with the matrix at 90 and 270 degrees, as ops.rotation_matrices does.
  *   quantize_u8 != 0: samples pass through uint8 as in train_galaxy.py:50-53 ((y*255).astype(uint8) in, /255 out);
  *             0: float32 'F' images as in train_particles.py:40-42.
  */
