@@ -1,5 +1,5 @@
 // The entry points of the analysis headers (include/svae_align.h, svae_ctfcorr.h, svae_frc.h, svae_refine.h, svae_classify.h,
-// svae_cluster.h, svae_gmm.h, svae_pca.h, svae_expect.h) and svae.h's svae_ctf_filter, which takes the same LDS / workspace
+// svae_cluster.h, svae_gmm.h, svae_pca.h, svae_expect.h, svae_eigen.h) and svae.h's svae_ctf_filter, which takes the same LDS / workspace
 // form.  Not a header of its own: api.hip includes it once, at namespace scope, below the kernels and its own fail(), Scope,
 // launch_status() and blocks_for().  The rules the entry points share are stated once, here at the top.
 
@@ -577,6 +577,149 @@ int svae_expect_sums_update(const double* contrib, const double* cover_w, const 
     hipLaunchKernelGGL(expect_sums_update_kernel, dim3(blocks_for((long)n_classes * N)), dim3(256), 0, st, contrib, cover_w,
                        reinterpret_cast<const int*>(cand), reinterpret_cast<const int*>(target), B, M, N, C, n_ref, n_classes, sum, count);
     return launch_status("svae_expect_sums_update");
+}
+
+// ---- per-class eigenimages of aligned images (include/svae_eigen.h) ----
+namespace {
+// the size rules the calls on a basis share; 0 or the refusal
+int eig_basis_check(const char* who, int32_t K, int64_t D, int32_t R) {
+    if (K < 1 || K > kEigMaxK || R < 1 || R > kEigMaxR || D < 1 || D > kEigMaxBasis || (int64_t)K * D * R > kEigMaxBasis)
+        return fail(SVAE_E_INVALID, "%s: bad sizes K=%d D=%lld R=%d (1 <= K <= %d, 1 <= R <= %d, 1 <= D, K D R <= 2^28)", who, K,
+                    (long long)D, R, kEigMaxK, kEigMaxR);
+    return SVAE_OK;
+}
+// the rules svae_eig_project and svae_eig_accumulate share: the sizes, then the images' pointers; 0 or the refusal
+int eig_images_check(const char* who, const void* aligned, const void* label, const void* mean, int32_t B, int32_t N, int32_t C,
+                     int32_t K, int32_t R) {
+    if (B < 1 || N < 1 || C < 1 || C > SVAE_MAX_OUT || (int64_t)B * N * C > 0x7fffffffLL)
+        return fail(SVAE_E_INVALID, "%s: bad sizes B=%d N=%d C=%d (C in 1..%d, B N C < 2^31)", who, B, N, C, SVAE_MAX_OUT);
+    if (const int rc = eig_basis_check(who, K, (int64_t)N * C, R)) return rc;
+    if (!aligned || !label || !mean) return fail(SVAE_E_INVALID, "%s: null aligned, label or mean", who);
+    if (misaligned8(mean)) return fail(SVAE_E_INVALID, "%s: mean must be 8-byte aligned", who);
+    return SVAE_OK;
+}
+// 0, or the refusal where the output `out` overlaps one of the inputs
+struct EigSpan {
+    const void* p;
+    size_t bytes;
+};
+int eig_overlap_check(const char* who, const char* what, const void* out, size_t out_bytes, std::initializer_list<EigSpan> inputs) {
+    for (const EigSpan& in : inputs)
+        if (in.p && bytes_overlap(in.p, in.bytes, out, out_bytes)) return fail(SVAE_E_INVALID, "%s: %s overlaps an input of the call", who, what);
+    return SVAE_OK;
+}
+}  // namespace
+
+int svae_eig_project(const float* aligned, const uint8_t* cover, const int32_t* label, const double* mean, const double* Q,
+                     int32_t B, int32_t N, int32_t C, int32_t K, int32_t R, double* T, svae_stream_t stream) {
+    const char* who = "svae_eig_project";
+    if (const int rc = eig_images_check(who, aligned, label, mean, B, N, C, K, R)) return rc;
+    if (!Q || !T) return fail(SVAE_E_INVALID, "%s: null Q or T", who);
+    if (misaligned8(Q) || misaligned8(T)) return fail(SVAE_E_INVALID, "%s: Q and T must be 8-byte aligned", who);
+    const size_t D = (size_t)N * C;
+    const std::initializer_list<EigSpan> inputs = {{aligned, (size_t)B * D * 4}, {cover, (size_t)B * N}, {label, (size_t)B * 4},
+                                                   {mean, (size_t)K * D * 8}, {Q, (size_t)K * D * R * 8}};
+    if (const int rc = eig_overlap_check(who, "T", T, (size_t)B * R * 8, inputs)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const EigGeo g{B, N, C, K, R, (long)D};
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(eig_project_kernel, dim3(B), dim3(256), 0, st, aligned, cover, reinterpret_cast<const int*>(label), mean, Q, g, T);
+    return launch_status(who);
+}
+
+int svae_eig_accumulate(const float* aligned, const uint8_t* cover, const int32_t* label, const double* mean, const double* T,
+                        int32_t B, int32_t N, int32_t C, int32_t K, int32_t R, double* Y, double* ssq, svae_stream_t stream) {
+    const char* who = "svae_eig_accumulate";
+    if (const int rc = eig_images_check(who, aligned, label, mean, B, N, C, K, R)) return rc;
+    if (!T || !Y) return fail(SVAE_E_INVALID, "%s: null T or Y", who);
+    if (misaligned8(T) || misaligned8(Y) || misaligned8(ssq)) return fail(SVAE_E_INVALID, "%s: T, Y and ssq must be 8-byte aligned", who);
+    const size_t D = (size_t)N * C;
+    const std::initializer_list<EigSpan> inputs = {{aligned, (size_t)B * D * 4}, {cover, (size_t)B * N}, {label, (size_t)B * 4},
+                                                   {mean, (size_t)K * D * 8}, {T, (size_t)B * R * 8}};
+    if (const int rc = eig_overlap_check(who, "Y", Y, (size_t)K * D * R * 8, inputs)) return rc;
+    if (ssq) {
+        if (const int rc = eig_overlap_check(who, "ssq", ssq, (size_t)K * D * 8, inputs)) return rc;
+        if (bytes_overlap(ssq, (size_t)K * D * 8, Y, (size_t)K * D * R * 8)) return fail(SVAE_E_INVALID, "%s: ssq overlaps Y", who);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const EigGeo g{B, N, C, K, R, (long)D};
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(eig_accumulate_kernel, dim3(blocks_for((long)K * D * R)), dim3(256), 0, st, aligned, cover,
+                       reinterpret_cast<const int*>(label), mean, T, g, Y, ssq);
+    return launch_status(who);
+}
+
+int svae_eig_orthonormalise(const double* Y, int32_t K, int64_t D, int32_t R, double* Q, svae_stream_t stream) {
+    const char* who = "svae_eig_orthonormalise";
+    if (const int rc = eig_basis_check(who, K, D, R)) return rc;
+    if (!Y || !Q) return fail(SVAE_E_INVALID, "%s: null Y or Q", who);
+    if (misaligned8(Y) || misaligned8(Q)) return fail(SVAE_E_INVALID, "%s: Y and Q must be 8-byte aligned", who);
+    const size_t basis = (size_t)K * D * R * 8;
+    if (const int rc = eig_overlap_check(who, "Q", Q, basis, {{Y, basis}})) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(eig_orthonormalise_kernel, dim3(K), dim3(256), 0, st, Y, (long)D, R, Q);
+    return launch_status(who);
+}
+
+int svae_eig_gram(const double* Q, const double* Y, const int64_t* members, int32_t K, int64_t D, int32_t R, double* G,
+                  svae_stream_t stream) {
+    const char* who = "svae_eig_gram";
+    if (const int rc = eig_basis_check(who, K, D, R)) return rc;
+    if (!Q || !Y || !members || !G) return fail(SVAE_E_INVALID, "%s: null Q, Y, members or G", who);
+    if (misaligned8(Q) || misaligned8(Y) || misaligned8(members) || misaligned8(G))
+        return fail(SVAE_E_INVALID, "%s: Q, Y, members and G must be 8-byte aligned", who);
+    const size_t basis = (size_t)K * D * R * 8;
+    if (const int rc = eig_overlap_check(who, "G", G, (size_t)K * R * R * 8, {{Q, basis}, {Y, basis}, {members, (size_t)K * 8}})) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(eig_gram_kernel, dim3(K * R), dim3(256), 0, st, Q, Y, reinterpret_cast<const long long*>(members), (long)D, R, G);
+    return launch_status(who);
+}
+
+int svae_eig_rotate(const double* Q, const double* Y, const double* W, const double* lambda, const int64_t* members, int32_t K,
+                    int64_t D, int32_t R, int32_t P, double* eigenimages, double* residual, double* rot, svae_stream_t stream) {
+    const char* who = "svae_eig_rotate";
+    if (const int rc = eig_basis_check(who, K, D, R)) return rc;
+    if (P < 1 || P > R) return fail(SVAE_E_INVALID, "%s: P = %d must be in 1..R = %d", who, P, R);
+    if (!Q || !Y || !W || !lambda || !members || !eigenimages || !residual || !rot)
+        return fail(SVAE_E_INVALID, "%s: null Q, Y, W, lambda, members, eigenimages, residual or rot", who);
+    if (misaligned8(Q) || misaligned8(Y) || misaligned8(W) || misaligned8(lambda) || misaligned8(members) || misaligned8(eigenimages) ||
+        misaligned8(residual) || misaligned8(rot))
+        return fail(SVAE_E_INVALID, "%s: every buffer must be 8-byte aligned", who);
+    const size_t basis = (size_t)K * D * R * 8;
+    const std::initializer_list<EigSpan> inputs = {{Q, basis}, {Y, basis}, {W, (size_t)K * R * R * 8}, {lambda, (size_t)K * R * 8},
+                                                   {members, (size_t)K * 8}};
+    const EigSpan outs[3] = {{eigenimages, (size_t)K * P * D * 8}, {residual, (size_t)K * P * 8}, {rot, (size_t)K * P * R * 8}};
+    const char* names[3] = {"eigenimages", "residual", "rot"};
+    for (int i = 0; i < 3; ++i) {
+        if (const int rc = eig_overlap_check(who, names[i], outs[i].p, outs[i].bytes, inputs)) return rc;
+        for (int j = 0; j < i; ++j)
+            if (bytes_overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes))
+                return fail(SVAE_E_INVALID, "%s: %s overlaps %s", who, names[i], names[j]);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(eig_rotate_kernel, dim3(K * P), dim3(256), 0, st, Q, Y, W, lambda, reinterpret_cast<const long long*>(members),
+                       (long)D, R, P, eigenimages, residual, rot);
+    return launch_status(who);
+}
+
+int svae_eig_coords(const double* T, const int32_t* label, const double* rot, int32_t B, int32_t K, int32_t R, int32_t P,
+                    double* coords, svae_stream_t stream) {
+    const char* who = "svae_eig_coords";
+    if (B < 1 || K < 1 || K > kEigMaxK || R < 1 || R > kEigMaxR || P < 1 || P > R)
+        return fail(SVAE_E_INVALID, "%s: bad sizes B=%d K=%d R=%d P=%d (1 <= K <= %d, 1 <= P <= R <= %d)", who, B, K, R, P, kEigMaxK, kEigMaxR);
+    if (!T || !label || !rot || !coords) return fail(SVAE_E_INVALID, "%s: null T, label, rot or coords", who);
+    if (misaligned8(T) || misaligned8(rot) || misaligned8(coords)) return fail(SVAE_E_INVALID, "%s: T, rot and coords must be 8-byte aligned", who);
+    if (const int rc = eig_overlap_check(who, "coords", coords, (size_t)B * P * 8,
+                                         {{T, (size_t)B * R * 8}, {label, (size_t)B * 4}, {rot, (size_t)K * P * R * 8}}))
+        return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(eig_coords_kernel, dim3(blocks_for((long)B * P)), dim3(256), 0, st, T, reinterpret_cast<const int*>(label), rot, B, K,
+                       R, P, coords);
+    return launch_status(who);
 }
 
 #undef POSE_KERNEL

@@ -6,6 +6,7 @@
 #include <string.h>
 #include <math.h>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <iterator>
 #include <type_traits>
@@ -23,6 +24,7 @@
 #include "../../include/svae_gmm.h"
 #include "../../include/svae_pca.h"
 #include "../../include/svae_expect.h"
+#include "../../include/svae_eigen.h"
 #include <hip/hip_ext.h>
 #include "dense.h"
 #include "wgrad2.h"
@@ -37,6 +39,7 @@
 #include "gmm.h"
 #include "pca.h"
 #include "expect.h"
+#include "eigen_images.h"
 #include "encoder.h"
 #include "split.h"
 

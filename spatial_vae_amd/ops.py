@@ -75,7 +75,7 @@ def _p(t):
 
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
-                 for name, (_, argtypes) in _lib.ALL_SIGNATURES.items()}
+                 for name, (_, argtypes) in _lib.BOUND_SIGNATURES.items()}
 
 
 def _call(name, device, *args):
@@ -1128,6 +1128,103 @@ class LatentPCA:
         _call("svae_pca_eigen", dev, out.cov, D, G, out.eigenvalues, out.components, out.sweeps, out.off_norm)
         _call("svae_pca_project", dev, points, N, D, G, P, group, out.count, out.mean, out.components, out.proj)
         return out
+
+
+EigenFit = namedtuple("EigenFit", "members ssq eigenvalues eigenimages residual coords sweeps off_norm")
+
+
+class EigenImages:
+    """The leading eigenimages of every class's aligned members about their class average (include/svae_eigen.h): block subspace
+    iteration with R columns per class, the covariance never formed.  start() takes the (K, D, R) start array; a pass is
+    begin_pass(), update() per minibatch in dataset order (svae_eig_project, svae_eig_accumulate) and end_pass() (the basis made
+    orthonormal again) -- or, after the last pass, finish() (svae_eig_gram, svae_pca_eigen, svae_eig_rotate, svae_eig_coords).
+    Every sum has a fixed order and nothing is atomic, so the same sequence of calls gives the same bits; nothing is read back."""
+
+    MAX_R = _lib.EIGEN_LIMITS["max_r"]
+    MAX_CLASSES = 4096
+    MAX_BASIS = 1 << 28         # K * D * R
+
+    def __init__(self, n_classes, N, C, R, device):
+        device = _hip_device("EigenImages", device)
+        self.K, self.N, self.C, self.R, self.device = int(n_classes), int(N), int(C), int(R), device
+        self.D = self.N * self.C
+        if not (1 <= self.K <= self.MAX_CLASSES and self.N >= 1 and 1 <= self.C <= _lib.MAX_OUT and 1 <= self.R <= self.MAX_R
+                and self.K * self.D * self.R <= self.MAX_BASIS):
+            raise RuntimeError("EigenImages: bad n_classes = %d, N = %d, C = %d or R = %d (n_classes <= %d, R <= %d, "
+                               "n_classes * N * C * R <= 2^28)" % (self.K, self.N, self.C, self.R, self.MAX_CLASSES, self.MAX_R))
+        f64 = dict(dtype=torch.float64, device=device)
+        self.Q = torch.empty(self.K, self.D, self.R, **f64)
+        self.Y = torch.zeros(self.K, self.D, self.R, **f64)
+        self.ssq = torch.zeros(self.K, self.D, **f64)
+        self.members = torch.zeros(self.K, dtype=torch.int64, device=device)
+        self._classes = torch.arange(self.K, dtype=torch.int32, device=device).unsqueeze(0)
+        self.passes, self._rows, self._labels = 0, [], []
+
+    def start(self, array):
+        """The basis of the first pass: `array` (K, D, R) float64 on the device, made orthonormal per class."""
+        _require_hip(array, "array")
+        if array.dtype != torch.float64 or tuple(array.shape) != (self.K, self.D, self.R) or not array.is_contiguous():
+            raise RuntimeError("EigenImages.start: the start array must be a contiguous (%d, %d, %d) float64 tensor, got %s %s"
+                               % (self.K, self.D, self.R, tuple(array.shape), array.dtype))
+        _call("svae_eig_orthonormalise", self.device, array, self.K, self.D, self.R, self.Q)
+
+    def begin_pass(self):
+        self.Y.zero_()
+        self._rows, self._labels = [], []
+
+    def update(self, aligned, cover, label, mean):
+        """One minibatch: aligned (B, N[, C]) fp32 and cover (B, N) uint8 or None as align_images returns them, label (B) int32,
+        -1 = in no class, mean (K, N, C) float64 the class averages.  The first pass also counts the members and sums the squares."""
+        for name, t in (("aligned", aligned), ("cover", cover), ("label", label), ("mean", mean)):
+            if t is not None:
+                _require_hip(t, name)
+        B = label.numel()
+        aligned = _f32(aligned)
+        if label.dtype != torch.int32 or (cover is not None and cover.dtype != torch.uint8) or mean.dtype != torch.float64:
+            raise RuntimeError("EigenImages.update: label must be int32, cover uint8 and mean float64")
+        if aligned.numel() != B * self.D or (cover is not None and cover.numel() != B * self.N) or mean.numel() != self.K * self.D:
+            raise RuntimeError("EigenImages.update: aligned %s / cover %s / mean %s do not fit %d images of %d pixels, %d channels in "
+                               "%d classes" % (tuple(aligned.shape), None if cover is None else tuple(cover.shape), tuple(mean.shape),
+                                               B, self.N, self.C, self.K))
+        first = self.passes == 0
+        T = torch.empty(B, self.R, dtype=torch.float64, device=self.device)
+        _call("svae_eig_project", self.device, aligned, cover, label, mean, self.Q, B, self.N, self.C, self.K, self.R, T)
+        _call("svae_eig_accumulate", self.device, aligned, cover, label, mean, T, B, self.N, self.C, self.K, self.R, self.Y,
+              self.ssq if first else None)
+        if first:
+            self.members += (label.unsqueeze(1) == self._classes).sum(0)
+        self._rows.append(T)
+        self._labels.append(label)
+
+    def end_pass(self):
+        """Between two passes: Q <- the orthonormalised Y."""
+        _call("svae_eig_orthonormalise", self.device, self.Y, self.K, self.D, self.R, self.Q)
+        self.passes += 1
+
+    def finish(self, P):
+        """After the last pass's updates (no end_pass): the Rayleigh-Ritz step.  Returns EigenFit of device tensors: members (K)
+        int64, ssq (K, D), eigenvalues (K, R) descending, eigenimages (K, P, D), residual (K, P), coords (images, P) in the order
+        of the last pass's updates, sweeps (K) int32 and off_norm (K) of svae_pca_eigen."""
+        K, D, R, P, dev = self.K, self.D, self.R, int(P), self.device
+        if not 1 <= P <= R:
+            raise RuntimeError("EigenImages.finish: P = %d must be in 1..%d" % (P, R))
+        if not self._rows:
+            raise RuntimeError("EigenImages.finish: no pass has been walked")
+        f64 = dict(dtype=torch.float64, device=dev)
+        G, W, lam = torch.empty(K, R, R, **f64), torch.empty(K, R, R, **f64), torch.empty(K, R, **f64)
+        sweeps, off_norm = torch.empty(K, dtype=torch.int32, device=dev), torch.empty(K, **f64)
+        _call("svae_eig_gram", dev, self.Q, self.Y, self.members, K, D, R, G)
+        step = LatentPCA.max_groups(R)
+        for lo in range(0, K, step):
+            g = min(step, K - lo)
+            _call("svae_pca_eigen", dev, G[lo:lo + g], R, g, lam[lo:lo + g], W[lo:lo + g], sweeps[lo:lo + g], off_norm[lo:lo + g])
+        images, residual, rot = torch.empty(K, P, D, **f64), torch.empty(K, P, **f64), torch.empty(K, P, R, **f64)
+        _call("svae_eig_rotate", dev, self.Q, self.Y, W, lam, self.members, K, D, R, P, images, residual, rot)
+        T, label = torch.cat(self._rows), torch.cat(self._labels)
+        coords = torch.empty(T.size(0), P, **f64)
+        _call("svae_eig_coords", dev, T, label, rot, T.size(0), K, R, P, coords)
+        self.passes += 1
+        return EigenFit(self.members, self.ssq, lam, images, residual, coords, sweeps, off_norm)
 
 
 def ctf_filter(table, n, m, scale=1.0, device=None):
