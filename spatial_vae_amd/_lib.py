@@ -258,6 +258,23 @@ EIGEN_LIMITS = {"max_r": 64, "dead_log2": -26}
 PENDING_HEADERS = {"svae_eigen.h": EIGEN_SIGNATURES}
 BOUND_SIGNATURES = dict(ALL_SIGNATURES, **{name: row for table in PENDING_HEADERS.values() for name, row in table.items()})
 
+# ---- include/svae_neighbours.h: latent-space neighbour averages, a thirteenth header with a table of its own ----
+# Same rules (tests/test_neighbours_cpu.py holds these rows to that header's prototypes).  The header's one constant is the
+# value of NEIGHBOUR_LIMITS, under SVAE_NBR_<NAME>.
+NEIGHBOUR_SIGNATURES = {
+    "svae_nbr_search": (cint, [vp, i32, i64, vp, i32, i64, i32, i32, vp, vp, vp]),
+    "svae_nbr_average": (cint, [vp, vp, i64, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
+}
+NEIGHBOUR_LIMITS = {"max_k": 256}
+
+# A third dict, because the two above are held to their exact present content by the tests that came with them: HEADERS to its
+# eleven rows, PENDING_HEADERS to svae_eigen.h alone and BOUND_SIGNATURES to the union of those two.  A header added since waits
+# here, bound and built like the others, until all of them move into HEADERS together with their rows of the shared stream
+# table; its side-stream and graph-replay checks live in its own GPU test meanwhile.  lib(), ops._POINTER_ARGS and
+# build.dependencies() walk this dict as well.
+WAITING_HEADERS = {"svae_neighbours.h": NEIGHBOUR_SIGNATURES}
+WAITING_SIGNATURES = {name: row for table in WAITING_HEADERS.values() for name, row in table.items()}
+
 
 def declared_in_header(header=None):
     """The function names include/svae.h (or another header of include/) declares (used by build() and the tests, never at
@@ -281,7 +298,7 @@ def lib():
         raise RuntimeError("spatial_vae_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
-    for name, (restype, argtypes) in BOUND_SIGNATURES.items():
+    for name, (restype, argtypes) in (*BOUND_SIGNATURES.items(), *WAITING_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

@@ -1,6 +1,6 @@
 // The entry points of the analysis headers (include/svae_align.h, svae_ctfcorr.h, svae_frc.h, svae_refine.h, svae_classify.h,
-// svae_cluster.h, svae_gmm.h, svae_pca.h, svae_expect.h, svae_eigen.h) and svae.h's svae_ctf_filter, which takes the same LDS / workspace
-// form.  Not a header of its own: api.hip includes it once, at namespace scope, below the kernels and its own fail(), Scope,
+// svae_cluster.h, svae_gmm.h, svae_pca.h, svae_expect.h, svae_eigen.h, svae_neighbours.h) and svae.h's svae_ctf_filter, which takes the
+// same LDS / workspace form.  Not a header of its own: api.hip includes it once, at namespace scope, below the kernels and its own fail(), Scope,
 // launch_status() and blocks_for().  The rules the entry points share are stated once, here at the top.
 
 namespace {
@@ -719,6 +719,53 @@ int svae_eig_coords(const double* T, const int32_t* label, const double* rot, in
     Scope prof(K_AUGMENT, st);
     hipLaunchKernelGGL(eig_coords_kernel, dim3(blocks_for((long)B * P)), dim3(256), 0, st, T, reinterpret_cast<const int*>(label), rot, B, K,
                        R, P, coords);
+    return launch_status(who);
+}
+
+// ---- latent-space neighbour averages (include/svae_neighbours.h) ----
+int svae_nbr_search(const double* query, int32_t B, int64_t query_base, const double* cand, int32_t M, int64_t cand_base, int32_t D,
+                    int32_t K, double* best_d2, int64_t* best_index, svae_stream_t stream) {
+    const char* who = "svae_nbr_search";
+    if (B < 1 || M < 1 || D < 1 || D > kNbrMaxD || K < 1 || K > kNbrMaxK || query_base < 0 || cand_base < 0)
+        return fail(SVAE_E_INVALID, "%s: bad sizes B=%d M=%d D=%d K=%d query_base=%lld cand_base=%lld (1 <= D <= %d, 1 <= K <= %d, "
+                    "1 <= B, 1 <= M, bases >= 0)", who, B, M, D, K, (long long)query_base, (long long)cand_base, kNbrMaxD, kNbrMaxK);
+    if (!query || !cand || !best_d2 || !best_index) return fail(SVAE_E_INVALID, "%s: null query, cand, best_d2 or best_index", who);
+    if (misaligned8(query) || misaligned8(cand) || misaligned8(best_d2) || misaligned8(best_index))
+        return fail(SVAE_E_INVALID, "%s: every buffer must be 8-byte aligned", who);
+    const size_t lists = (size_t)B * K * 8;
+    const std::initializer_list<EigSpan> inputs = {{query, (size_t)B * D * 8}, {cand, (size_t)M * D * 8}};
+    if (const int rc = eig_overlap_check(who, "best_d2", best_d2, lists, inputs)) return rc;
+    if (const int rc = eig_overlap_check(who, "best_index", best_index, lists, inputs)) return rc;
+    if (bytes_overlap(best_d2, lists, best_index, lists)) return fail(SVAE_E_INVALID, "%s: best_d2 overlaps best_index", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(nbr_search_kernel, dim3((B + kNbrQueries - 1) / kNbrQueries), dim3(256), 0, st, query, B, (long long)query_base, cand,
+                       M, (long long)cand_base, D, K, best_d2, reinterpret_cast<long long*>(best_index));
+    return launch_status(who);
+}
+
+int svae_nbr_average(const float* stack, const uint8_t* cover, int64_t images, int32_t N, int32_t C, const int64_t* index,
+                     const double* weight, int32_t B, int32_t T, float* average, double* support, svae_stream_t stream) {
+    const char* who = "svae_nbr_average";
+    if (images < 1 || images > 0x7fffffffLL || N < 1 || C < 1 || C > SVAE_MAX_OUT || (int64_t)N * C > 0x7fffffffLL || B < 1 || T < 1 ||
+        T > kNbrMaxT)
+        return fail(SVAE_E_INVALID, "%s: bad sizes images=%lld N=%d C=%d B=%d T=%d (1 <= images < 2^31, C in 1..%d, N C < 2^31, 1 <= B, "
+                    "T in 1..%d)", who, (long long)images, N, C, B, T, SVAE_MAX_OUT, kNbrMaxT);
+    if (!stack || !index || !average) return fail(SVAE_E_INVALID, "%s: null stack, index or average", who);
+    if (misaligned8(index) || misaligned8(weight) || misaligned8(support))
+        return fail(SVAE_E_INVALID, "%s: index, weight and support must be 8-byte aligned", who);
+    const size_t D = (size_t)N * C, slots = (size_t)B * T * 8;
+    const std::initializer_list<EigSpan> inputs = {{stack, (size_t)images * D * 4}, {cover, (size_t)images * N}, {index, slots},
+                                                   {weight, slots}};
+    if (const int rc = eig_overlap_check(who, "average", average, (size_t)B * D * 4, inputs)) return rc;
+    if (support) {
+        if (const int rc = eig_overlap_check(who, "support", support, (size_t)B * N * 8, inputs)) return rc;
+        if (bytes_overlap(support, (size_t)B * N * 8, average, (size_t)B * D * 4)) return fail(SVAE_E_INVALID, "%s: support overlaps average", who);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Scope prof(K_AUGMENT, st);
+    hipLaunchKernelGGL(nbr_average_kernel, dim3(B), dim3(256), 0, st, stack, cover, (long long)images, N, C,
+                       reinterpret_cast<const long long*>(index), weight, T, average, support);
     return launch_status(who);
 }
 

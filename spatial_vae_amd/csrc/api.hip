@@ -40,6 +40,7 @@
 #include "pca.h"
 #include "expect.h"
 #include "eigen_images.h"
+#include "neighbours.h"
 #include "encoder.h"
 #include "split.h"
 

@@ -108,9 +108,10 @@ def eigen_arguments(argv=None):
     return args
 
 
-def stored_poses(args, facts):
+def stored_poses(args, facts, _refuse=_refuse):
     """The (images, 3) float32 poses theta, dx0, dx1 of the chosen estimate out of the score file, in the decoder's units: a
-    coordinate the model does not infer is 0.  Refuses a file whose image count or pose arrays do not fit the split."""
+    coordinate the model does not infer is 0.  Refuses a file whose image count or pose arrays do not fit the split (through
+    `_refuse`: another script that reads the same files refuses under its own name)."""
     arrays, images = args.score_arrays, facts.images
     if args.score_meta.get("images") != images:
         _refuse("--scores {} holds {} images, the {} split has {}".format(args.scores, args.score_meta.get("images"), facts.split, images))

@@ -75,7 +75,7 @@ def _p(t):
 
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
-                 for name, (_, argtypes) in _lib.BOUND_SIGNATURES.items()}
+                 for name, (_, argtypes) in (*_lib.BOUND_SIGNATURES.items(), *_lib.WAITING_SIGNATURES.items())}
 
 
 def _call(name, device, *args):
@@ -1225,6 +1225,68 @@ class EigenImages:
         _call("svae_eig_coords", dev, T, label, rot, T.size(0), K, R, P, coords)
         self.passes += 1
         return EigenFit(self.members, self.ssq, lam, images, residual, coords, sweeps, off_norm)
+
+
+class NeighbourSearch:
+    """The running lists of every image's K nearest neighbours under the order (squared distance, image index)
+    (svae_nbr_search, include/svae_neighbours.h): d2 (images, K) float64 and index (images, K) int64 on the device, filled with
+    the empty slot (+inf, -1).  update() offers the images cand_base.. to the images query_base..; the lists are a property of
+    the set offered, whatever the split into calls.  Nothing is read back."""
+
+    MAX_K = _lib.NEIGHBOUR_LIMITS["max_k"]
+    MAX_D = 512
+
+    def __init__(self, images, K, device):
+        device = _hip_device("NeighbourSearch", device)
+        self.images, self.K, self.device = int(images), int(K), device
+        if self.images < 1 or not 1 <= self.K <= self.MAX_K:
+            raise RuntimeError("NeighbourSearch: bad images = %d or K = %d (K in 1..%d)" % (self.images, self.K, self.MAX_K))
+        self.d2 = torch.full((self.images, self.K), float("inf"), dtype=torch.float64, device=device)
+        self.index = torch.full((self.images, self.K), -1, dtype=torch.int64, device=device)
+
+    def update(self, query, query_base, cand, cand_base):
+        """One call: query (B, D) and cand (M, D) float64 contiguous on the device, the latents of the images query_base .. and
+        cand_base ..; the rows query_base .. query_base + B - 1 of the lists are updated."""
+        _require_hip(query, "query")
+        _require_hip(cand, "cand")
+        q0, c0 = int(query_base), int(cand_base)
+        if (query.dtype != torch.float64 or cand.dtype != torch.float64 or query.dim() != 2 or cand.dim() != 2
+                or query.size(1) != cand.size(1) or not 1 <= query.size(1) <= self.MAX_D or query.size(0) < 1 or cand.size(0) < 1):
+            raise RuntimeError("NeighbourSearch.update: query %s %s and cand %s %s must be float64 (B, D) and (M, D) with D in 1..%d"
+                               % (tuple(query.shape), query.dtype, tuple(cand.shape), cand.dtype, self.MAX_D))
+        B = query.size(0)
+        if q0 < 0 or c0 < 0 or q0 + B > self.images:
+            raise RuntimeError("NeighbourSearch.update: the queries %d .. %d are not among the %d images" % (q0, q0 + B - 1, self.images))
+        _call("svae_nbr_search", self.device, query, B, q0, cand, cand.size(0), c0, query.size(1), self.K, self.d2[q0:q0 + B],
+              self.index[q0:q0 + B])
+
+    def lists(self):
+        """(d2, index): the device tensors."""
+        return self.d2, self.index
+
+
+def neighbour_average(stack, cover, index, weight=None, support=False):
+    """svae_nbr_average: stack (images, N[, C]) fp32 and cover (images, N) uint8 or None as align_images returns them, index
+    (B, T) int64 with -1 for an empty slot, weight (B, T) float64 or None for all 1.  Returns average (B, N, C) fp32, and with
+    support=True (average, support (B, N) float64): device tensors."""
+    for name, t in (("stack", stack), ("cover", cover), ("index", index), ("weight", weight)):
+        if t is not None:
+            _require_hip(t, name)
+    if stack.dim() == 2:
+        stack = stack.unsqueeze(2)
+    if stack.dtype != torch.float32 or stack.dim() != 3 or index.dtype != torch.int64 or index.dim() != 2:
+        raise RuntimeError("neighbour_average: stack must be float32 (images, N, C) and index int64 (B, T), got %s %s and %s %s"
+                           % (tuple(stack.shape), stack.dtype, tuple(index.shape), index.dtype))
+    images, N, C = stack.shape
+    B, T = index.shape
+    if cover is not None and (cover.dtype != torch.uint8 or tuple(cover.shape) != (images, N)):
+        raise RuntimeError("neighbour_average: cover must be uint8 (%d, %d), got %s %s" % (images, N, tuple(cover.shape), cover.dtype))
+    if weight is not None and (weight.dtype != torch.float64 or tuple(weight.shape) != (B, T)):
+        raise RuntimeError("neighbour_average: weight must be float64 (%d, %d), got %s %s" % (B, T, tuple(weight.shape), weight.dtype))
+    average = torch.empty(B, N, C, dtype=torch.float32, device=stack.device)
+    sup = torch.empty(B, N, dtype=torch.float64, device=stack.device) if support else None
+    _call("svae_nbr_average", stack.device, stack, cover, images, N, C, index, weight, B, T, average, sup)
+    return (average, sup) if support else average
 
 
 def ctf_filter(table, n, m, scale=1.0, device=None):
