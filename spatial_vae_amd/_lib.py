@@ -228,16 +228,6 @@ PCA_SIGNATURES = {
 }
 
 
-# ---- the one list of the headers of include/, in the order they were added: header -> its table above ----
-# lib(), ops._POINTER_ARGS, build.dependencies() and __graft_entry__.build() walk it; a twelfth header is one more row.
-HEADERS = {
-    "svae.h": SIGNATURES, "svae_stream.h": STREAM_SIGNATURES, "svae_align.h": ALIGN_SIGNATURES,
-    "svae_ctfcorr.h": CTFCORR_SIGNATURES, "svae_cluster.h": CLUSTER_SIGNATURES, "svae_frc.h": FRC_SIGNATURES,
-    "svae_refine.h": REFINE_SIGNATURES, "svae_classify.h": CLASSIFY_SIGNATURES, "svae_gmm.h": GMM_SIGNATURES,
-    "svae_expect.h": EXPECT_SIGNATURES, "svae_pca.h": PCA_SIGNATURES,
-}
-ALL_SIGNATURES = {name: row for table in HEADERS.values() for name, row in table.items()}
-
 # ---- include/svae_eigen.h: per-class eigenimages of aligned images, a twelfth header with a table of its own ----
 # Same rules (tests/test_eigen_cpu.py holds these rows to that header's prototypes).  The header's two constants are the values
 # of EIGEN_LIMITS, under SVAE_EIG_<NAME>.
@@ -251,12 +241,6 @@ EIGEN_SIGNATURES = {
 }
 EIGEN_LIMITS = {"max_r": 64, "dead_log2": -26}
 
-# Headers whose entry points are bound and built like those of HEADERS but are not yet rows of it: every stream-taking function
-# of ALL_SIGNATURES must have a row in the tests' shared stream table, and svae_eigen.h's side-stream and graph-replay checks
-# still live in its own GPU test.  The header moves into HEADERS together with its stream-table rows.  lib(),
-# ops._POINTER_ARGS and build.dependencies() walk both dicts.
-PENDING_HEADERS = {"svae_eigen.h": EIGEN_SIGNATURES}
-BOUND_SIGNATURES = dict(ALL_SIGNATURES, **{name: row for table in PENDING_HEADERS.values() for name, row in table.items()})
 
 # ---- include/svae_neighbours.h: latent-space neighbour averages, a thirteenth header with a table of its own ----
 # Same rules (tests/test_neighbours_cpu.py holds these rows to that header's prototypes).  The header's one constant is the
@@ -267,13 +251,19 @@ NEIGHBOUR_SIGNATURES = {
 }
 NEIGHBOUR_LIMITS = {"max_k": 256}
 
-# A third dict, because the two above are held to their exact present content by the tests that came with them: HEADERS to its
-# eleven rows, PENDING_HEADERS to svae_eigen.h alone and BOUND_SIGNATURES to the union of those two.  A header added since waits
-# here, bound and built like the others, until all of them move into HEADERS together with their rows of the shared stream
-# table; its side-stream and graph-replay checks live in its own GPU test meanwhile.  lib(), ops._POINTER_ARGS and
-# build.dependencies() walk this dict as well.
-WAITING_HEADERS = {"svae_neighbours.h": NEIGHBOUR_SIGNATURES}
-WAITING_SIGNATURES = {name: row for table in WAITING_HEADERS.values() for name, row in table.items()}
+
+# ---- the one list of the headers of include/, in the order they were added: header -> its table above ----
+# lib(), ops._POINTER_ARGS, build.dependencies() and __graft_entry__.build() walk it; a fourteenth header is one more row.
+# tests/test_binding_cpu.py holds every row to its header's prototypes by one rule (the test files named above: what is a
+# header's own), and every function here that takes a stream has a row in the tests' shared stream table.
+HEADERS = {
+    "svae.h": SIGNATURES, "svae_stream.h": STREAM_SIGNATURES, "svae_align.h": ALIGN_SIGNATURES,
+    "svae_ctfcorr.h": CTFCORR_SIGNATURES, "svae_cluster.h": CLUSTER_SIGNATURES, "svae_frc.h": FRC_SIGNATURES,
+    "svae_refine.h": REFINE_SIGNATURES, "svae_classify.h": CLASSIFY_SIGNATURES, "svae_gmm.h": GMM_SIGNATURES,
+    "svae_expect.h": EXPECT_SIGNATURES, "svae_pca.h": PCA_SIGNATURES, "svae_eigen.h": EIGEN_SIGNATURES,
+    "svae_neighbours.h": NEIGHBOUR_SIGNATURES,
+}
+ALL_SIGNATURES = {name: row for table in HEADERS.values() for name, row in table.items()}
 
 
 def declared_in_header(header=None):
@@ -298,7 +288,7 @@ def lib():
         raise RuntimeError("spatial_vae_amd: %s is missing -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or spatial_vae_amd.build()); there is no fallback implementation" % path)
     L = ctypes.CDLL(path)
-    for name, (restype, argtypes) in (*BOUND_SIGNATURES.items(), *WAITING_SIGNATURES.items()):
+    for name, (restype, argtypes) in ALL_SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.svae_abi_version() != ABI_VERSION:

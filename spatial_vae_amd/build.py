@@ -13,11 +13,9 @@ def library_path():
 
 
 def dependencies():
-    """Every file the library is built from: csrc/ and the headers of include/ that _lib.HEADERS, _lib.PENDING_HEADERS and
-    _lib.WAITING_HEADERS list."""
-    from ._lib import HEADERS, PENDING_HEADERS, WAITING_HEADERS   # not at import: _lib imports this module
-    return [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(_HERE, "..", "include", h)
-                                                         for h in (*HEADERS, *PENDING_HEADERS, *WAITING_HEADERS)]
+    """Every file the library is built from: csrc/ and the headers of include/ that _lib.HEADERS lists."""
+    from ._lib import HEADERS   # not at import: _lib imports this module
+    return [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(_HERE, "..", "include", h) for h in HEADERS]
 
 
 def _stale():

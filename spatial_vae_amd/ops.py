@@ -75,7 +75,7 @@ def _p(t):
 
 # per entry point, the positions of its device-pointer arguments (the trailing stream aside): what _call takes tensors for
 _POINTER_ARGS = {name: tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.vp)
-                 for name, (_, argtypes) in (*_lib.BOUND_SIGNATURES.items(), *_lib.WAITING_SIGNATURES.items())}
+                 for name, (_, argtypes) in _lib.ALL_SIGNATURES.items()}
 
 
 def _call(name, device, *args):

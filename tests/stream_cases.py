@@ -870,8 +870,8 @@ class PowerAndWiener(Case):
 CTF_LDS_PAIR = (10, 9)
 CTF_GLOBAL_PAIR = (88, 87)
 
-# the rows of the analysis headers (k-means, mixture, PCA, ring correlation, pose search, classification, soft averages) live in
-# a sibling file that subclasses Case, so it is imported here, below everything it needs
+# the rows of the analysis headers (k-means, mixture, PCA, ring correlation, pose search, classification, soft averages,
+# eigenimages, neighbour averages) live in a sibling file that subclasses Case, so it is imported here, below everything it needs
 from stream_cases_analysis import analysis_cases            # noqa: E402
 
 

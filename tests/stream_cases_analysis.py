@@ -1,6 +1,7 @@
 """The rows of tests/stream_cases.py's table for the analysis headers (include/svae_cluster.h, _frc.h, _refine.h, _classify.h,
-_gmm.h, _expect.h, _pca.h): one row per header, at the smallest shapes that exercise the three-chunk tail (N = 600), the
-odd-by-odd plane and the LDS form.  stream_cases.make_cases() appends analysis_cases(); import stream_cases, not this file.
+_gmm.h, _expect.h, _pca.h, _eigen.h, _neighbours.h): one row per header (two for the eigenimage chain), at the smallest shapes
+that exercise the three-chunk tail (N = 600), the odd-by-odd plane and the LDS form, and for the last two headers at the shapes
+of their own GPU tests.  stream_cases.make_cases() appends analysis_cases(); import stream_cases, not this file.
 
 Every check here takes the seed: the baselines of BOTH input sets are held to the header's float64 reference."""
 import functools
@@ -8,10 +9,12 @@ import functools
 import numpy as np
 
 import classify_ref as CR
+import eigen_ref as ER
 import expect_ref as X
 import frc_ref as F
 import gmm_ref as G
 import kmeans_ref as K
+import neighbours_ref as NR
 import pca_ref as PR
 import refine_ref as R
 import stream_cases as S
@@ -349,6 +352,111 @@ class PcaCase(S.Case):
             assert np.abs(out[key] - want[key]).max() <= 1e-10 * max(1.0, np.abs(want[key]).max()), key
 
 
+@functools.lru_cache(maxsize=None)
+def _eigen_inputs(case):
+    """The inputs of one chain of tests/test_gpu_eigen.py, built as its reference() builds them.  Shared: treat as read-only."""
+    seed, B, rows, cols, C, K, Rc, P, covered = case
+    aligned, cover, label = ER.images(seed, B, rows, cols, C, K, covered)
+    label64, D = label.astype(np.int64), rows * cols * C
+    return {"aligned": aligned, "cover": cover, "class_of": label, "mean": ER.class_moments(aligned, cover, label64, K)[0].reshape(K, D),
+            "members": np.array([(label64 == k).sum() for k in range(K)], np.int64), "start": ER.start_array(seed + 100, K, D, Rc),
+            "Y": np.zeros((K, D, Rc)), "ssq": np.zeros((K, D))}
+
+
+class EigenCase(S.Case):
+    """The whole chain of tests/test_gpu_eigen.py's Run.chain at one of its CASES: orthonormalise, project, accumulate,
+    orthonormalise, gram, svae_pca_eigen (one call: K is far below its group limit), rotate, coords.  Y and ssq are the calls'
+    to add to: state, and zero in both sets.  The labels (with their -1 and K + 1) and the member counts depend on B and K
+    alone, so they are the same in both sets; set B is the same fixture builder with another seed."""
+    entry_points = ("svae_eig_orthonormalise", "svae_eig_project", "svae_eig_accumulate", "svae_eig_gram", "svae_pca_eigen",
+                    "svae_eig_rotate", "svae_eig_coords")
+    has_reference = True
+    state, same_in_both_sets, must_differ = ("Y", "ssq"), ("Y", "ssq", "class_of", "members"), ("T", "eigenimages")
+
+    def __init__(self, case):
+        self.case = case
+        _, self.B, rows, cols, self.C, self.K, self.R, self.P, _ = case
+        self.N = rows * cols
+        self.D = self.N * self.C
+        self.name = "eigen_B%d_%dx%dx%d_K%d_R%d_P%d" % case[1:8]
+
+    def fixture(self, seed):
+        return (self.case[0] + 20 * seed,) + self.case[1:]
+
+    def inputs(self, seed):
+        return dict(_eigen_inputs(self.fixture(seed)))
+
+    def _outputs(self):
+        K, D, Rc, P, B, f8 = self.K, self.D, self.R, self.P, self.B, np.float64
+        return {"Q0": ((K, D, Rc), f8), "T": ((B, Rc), f8), "Q1": ((K, D, Rc), f8), "G": ((K, Rc, Rc), f8), "lambda": ((K, Rc), f8),
+                "W": ((K, Rc, Rc), f8), "sweeps": ((K,), np.int32), "off_norm": ((K,), f8), "eigenimages": ((K, P, D), f8),
+                "residual": ((K, P), f8), "rot": ((K, P, Rc), f8), "coords": ((B, P), f8)}
+
+    def steps(self):
+        p, L = self.ptr, self.L
+        B, N, C, K, Rc, P, D = self.B, self.N, self.C, self.K, self.R, self.P, self.D
+        images = lambda: (p("aligned"), p("cover"), p("class_of"), p("mean"))
+        return [lambda st: L.svae_eig_orthonormalise(p("start"), K, D, Rc, p("Q0"), st),
+                lambda st: L.svae_eig_project(*images(), p("Q0"), B, N, C, K, Rc, p("T"), st),
+                lambda st: L.svae_eig_accumulate(*images(), p("T"), B, N, C, K, Rc, p("Y"), p("ssq"), st),
+                lambda st: L.svae_eig_orthonormalise(p("Y"), K, D, Rc, p("Q1"), st),
+                lambda st: L.svae_eig_gram(p("Q0"), p("Y"), p("members"), K, D, Rc, p("G"), st),
+                lambda st: L.svae_pca_eigen(p("G"), Rc, K, p("lambda"), p("W"), p("sweeps"), p("off_norm"), st),
+                lambda st: L.svae_eig_rotate(p("Q0"), p("Y"), p("W"), p("lambda"), p("members"), K, D, Rc, P, p("eigenimages"),
+                                             p("residual"), p("rot"), st),
+                lambda st: L.svae_eig_coords(p("T"), p("class_of"), p("rot"), B, K, Rc, P, p("coords"), st)]
+
+    def check(self, out, seed=0):
+        """tests/eigen_ref.py within tests/test_gpu_eigen.py's BOUND, through that file's chain_errors: what hangs on an
+        eigenvector is compared where its eigenvalue is separated."""
+        from test_gpu_eigen import BOUND, chain_errors, reference
+        want = reference(self.fixture(seed))[1]
+        errs, _ = chain_errors(out, want, self.inputs(seed)["class_of"], self.K, self.R, self.P)
+        assert not {k: e for k, e in errs.items() if not e <= BOUND}, (self.name, errs)
+
+
+class NeighbourCase(S.Case):
+    """svae_nbr_search on tests/test_gpu_neighbours.py's 300 x 7 latents, K = 64, the candidates offered in three chunks out of
+    order, then svae_nbr_average on its 40 x 105 x 3 stack (B = 17, T = 257: repeated images, empty slots, indices that are
+    skipped) with weight and support.  The lists are the search's to update: state, and (+inf, -1) in both sets."""
+    name, entry_points, has_reference = "neighbours_300x7_K64_avg_40x105x3_T257", ("svae_nbr_search", "svae_nbr_average"), True
+    state, same_in_both_sets, non_finite_inputs, must_differ = ("d2", "index"), ("d2", "index"), ("d2",), ("d2", "average")
+    chunks = ((70, 300), (0, 64), (64, 70))
+    Q, D, K = 300, 7, 64                                    # queries (all of them candidates too), coordinates, list length
+    images, N, C, B, T = 40, 105, 3, 17, 257                # of the stack; a slot outside [0, images) is skipped
+
+    def fixtures(self, seed):
+        from test_gpu_neighbours import average_case, search_case
+        return search_case("300x7_K64", seed), average_case("40x105x3_T257", seed)
+
+    def inputs(self, seed):
+        (z, K, _, _), (stack, cover, slots, weight, _, _, _) = self.fixtures(seed)
+        d2, index = NR.empty_lists(z.shape[0], K)
+        return {"z": z.copy(), "d2": d2, "index": index, "stack": stack.copy(), "cover": cover.copy(), "slots": slots.copy(),
+                "weight": weight.copy()}                    # copies: the fixtures are shared and read-only
+
+    def _outputs(self):
+        return {"average": ((self.B, self.N, self.C), np.float32), "support": ((self.B, self.N), np.float64)}
+
+    def steps(self):
+        p, L = self.ptr, self.L
+        Q, D, K, images, N, C, B, T = self.Q, self.D, self.K, self.images, self.N, self.C, self.B, self.T
+        search = [lambda st, lo=lo, hi=hi: L.svae_nbr_search(p("z"), Q, 0, p("z") + lo * D * 8, hi - lo, lo, D, K, p("d2"), p("index"), st)
+                  for lo, hi in self.chunks]
+        return search + [lambda st: L.svae_nbr_average(p("stack"), p("cover"), images, N, C, p("slots"), p("weight"), B, T, p("average"),
+                                                       p("support"), st)]
+
+    def check(self, out, seed=0):
+        """The lists and the support bit for bit (neighbours_ref.brute_force, neighbours_ref.average), the averages within one
+        float32 of the reference's quotient: the bounds of tests/test_gpu_neighbours.py."""
+        (_, _, want_d, want_i), (_, _, _, _, _, want_sup, exact) = self.fixtures(seed)
+        assert out["d2"].tobytes() == want_d.tobytes() and out["index"].tobytes() == want_i.tobytes()
+        assert out["support"].tobytes() == want_sup.tobytes()
+        assert NR.within_one_float(out["average"], exact)[0].all()
+
+
 def analysis_cases():
     """Fresh, unallocated instances in a fixed order.  Construction is cheap: the data are built, once, by inputs()."""
-    return [KMeansCase(), GmmCase(), PcaCase(), FrcCase(), RefineCase(), ClassifyCase(), ExpectCase()]
+    from test_gpu_eigen import CASES
+    return [KMeansCase(), GmmCase(), PcaCase(), FrcCase(), RefineCase(), ClassifyCase(), ExpectCase(), EigenCase(CASES[1]),
+            EigenCase(CASES[7]), NeighbourCase()]

@@ -180,6 +180,64 @@ def test_loaded_library_carries_the_table():
         assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
 
 
+# ---------------------------------------------------------------- the headers added since: one rule for all of them
+THIRTEEN = ["svae.h", "svae_stream.h", "svae_align.h", "svae_ctfcorr.h", "svae_cluster.h", "svae_frc.h", "svae_refine.h",
+            "svae_classify.h", "svae_gmm.h", "svae_expect.h", "svae_pca.h", "svae_eigen.h", "svae_neighbours.h"]
+# the file of csrc/ that holds a header's kernels, where it is not the header's name without its prefix
+CSRC = {"svae_stream.h": "iw_stream.h", "svae_eigen.h": "eigen_images.h"}
+
+
+def parse_added_header(name):
+    """(path, parse_header of include/<name> without its #include "svae.h")."""
+    path = os.path.join(ROOT, "include", name)
+    with open(path) as f:
+        return path, parse_header(f.read().replace('#include "svae.h"', ""))
+
+
+def test_headers_is_the_one_list_in_the_order_the_headers_were_added():
+    B = _binding()
+    assert list(B.HEADERS) == THIRTEEN
+    assert list(B.ALL_SIGNATURES) == [name for table in B.HEADERS.values() for name in table] and len(B.ALL_SIGNATURES) == 76
+
+
+@pytest.mark.parametrize("name", THIRTEEN[1:])
+def test_added_header_binding_matches_its_header(name):
+    """What every header added to svae.h is held to (svae.h itself: compare() above).  The header declares exactly the functions
+    of its table in _lib.HEADERS, which no other table has; return type and arguments agree type by type under the rules used
+    for svae.h, a pointer to a struct the header declares itself being the address of a record in device memory (c_void_p); an
+    entry point that takes a stream calls it `stream`; the loaded library carries the table; ops._POINTER_ARGS knows every name;
+    the header and its file of csrc/ are files the library is built from, so an edit of either makes it stale.  The per-header
+    files hold what is a header's own: the number of functions, constants, struct mirrors, argument names, pointer positions."""
+    import sys
+
+    import stream_cases
+    from spatial_vae_amd import ops
+    B = _binding()
+    build = sys.modules["spatial_vae_amd.build"]        # the module: the package's attribute of that name is its build()
+    table = B.HEADERS[name]
+    path, H = parse_added_header(name)
+    assert set(H["functions"]) == set(table) == set(B.declared_in_header(path)) and table
+    assert all(not set(t) & set(table) for h, t in B.HEADERS.items() if h != name)
+    takes_stream = set(stream_cases.stream_entry_points())
+    for fn, ((rbase, rptr), args) in H["functions"].items():
+        restype, argtypes = table[fn]
+        assert restype in _allowed(rbase, rptr, B), fn
+        assert len(args) == len(argtypes), fn
+        for (base, pointer, arg), have in zip(args, argtypes):
+            assert have in _allowed(base, pointer, B, device_record=base in H["structs"]), (fn, arg)
+        assert (args[-1][2] == "stream") == (fn in takes_stream) if args else fn not in takes_stream, fn
+    L = B.lib()
+    for fn, (restype, argtypes) in table.items():
+        have = getattr(L, fn)
+        assert have.restype is restype and list(have.argtypes) == list(argtypes), fn
+    assert L.svae_abi_version() == B.ABI_VERSION == 2
+    assert set(table) <= set(ops._POINTER_ARGS)
+    deps = build.dependencies()
+    assert all(os.path.isfile(d) for d in deps)
+    for needed in (path, os.path.join(ROOT, "spatial_vae_amd", "csrc", CSRC.get(name, name[len("svae_"):]))):
+        assert any(os.path.samefile(needed, d) for d in deps), needed
+
+
 @pytest.mark.parametrize("what, alter, named", [
     ("two arguments swapped", lambda t: t.replace("float eps, int64_t step, int32_t zero_grad", "int64_t step, float eps, int32_t zero_grad"),
      "function svae_adam_step:"),

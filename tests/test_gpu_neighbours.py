@@ -1,8 +1,9 @@
 """The neighbour kernels (include/svae_neighbours.h) on the MI355X, through ctypes alone, against the float64 restatement
 tests/neighbours_ref.py: the lists bit for bit (only subtraction, multiplication and addition are involved), whatever the split
 of candidates and queries into calls; the averages within one float32 of the reference's single division, their support bit
-for bit.  Every buffer the calls write sits inside guard bytes (decoder_abi.Guarded).  The header is not in the shared stream
-table, so its side-stream and graph-replay checks are here."""
+for bit.  Every buffer the calls write sits inside guard bytes (decoder_abi.Guarded).  The side-stream and graph-replay checks
+are the shared stream table's (tests/stream_cases_analysis.py), whose row runs search_case("300x7_K64") and
+average_case("40x105x3_T257"), each with a second seed for its other input set."""
 import ctypes
 import functools
 
@@ -79,9 +80,9 @@ SEARCH = ["lattice", "300x7_K64", "70x1_K1", "40x33_K256", "1000x3_K100_duplicat
 
 
 @functools.lru_cache(maxsize=None)
-def search_case(name):
-    """(latents, K, reference d2, reference index): the reference is the full sort, made once."""
-    rs = np.random.RandomState(SEARCH.index(name) + 10)
+def search_case(name, seed=0):
+    """(latents, K, reference d2, reference index): the reference is the full sort, made once.  The tests here use seed 0."""
+    rs = np.random.RandomState(SEARCH.index(name) + 10 + 100 * seed)
     if name == "lattice":
         z, K = R.lattice(), 5
     elif name == "300x7_K64":
@@ -170,9 +171,9 @@ AVERAGE = ["60x35x1_T6", "40x105x3_T257", "10x1x4_T1"]
 
 
 @functools.lru_cache(maxsize=None)
-def average_case(name):
-    """(stack, cover, index, weight, reference average, reference support, unrounded quotient)."""
-    rs = np.random.RandomState(AVERAGE.index(name) + 30)
+def average_case(name, seed=0):
+    """(stack, cover, index, weight, reference average, reference support, unrounded quotient).  The tests here use seed 0."""
+    rs = np.random.RandomState(AVERAGE.index(name) + 30 + 100 * seed)
     if name == "60x35x1_T6":
         images, N, C, B, T = 60, 35, 1, 60, 6
         index = np.concatenate([np.arange(60)[:, None], rs.randint(0, images, (B, T - 1))], 1)
@@ -249,44 +250,7 @@ def test_a_non_finite_pixel_reaches_exactly_the_rows_that_list_it():
     assert np.isnan(got[hit]).all() and _same_bytes(got[~hit], avg[~hit]) and _same_bytes(got_sup, sup)
 
 
-# ---------------------------------------------------------------- both entries: streams, graphs, refusals, the wrappers
-def test_side_stream_and_graph_replay_are_bit_equal():
-    """Both entries on a non-default stream, and captured into a graph and replayed twice with the lists refilled before each
-    replay: bit-equal to the default stream's."""
-    z, K, want_d, want_i = search_case("300x7_K64")
-    stack, cover, index, weight, _, _, _ = average_case("40x105x3_T257")
-    chunks = [(70, 300), (0, 64), (64, 70)]
-    first = Average(stack, cover, index, weight)
-    assert first.call() == 0
-    avg, sup = first.read()
-    side = torch.cuda.Stream(_dev())
-    torch.cuda.synchronize()
-    with torch.cuda.stream(side):
-        st = ctypes.c_void_p(side.cuda_stream)
-        s, a = Search(z, K), Average(stack, cover, index, weight)
-        side.synchronize()
-        s.run(chunks, st=st)
-        assert a.call(st=st) == 0
-    side.synchronize()
-    got_d, got_i = s.read()
-    assert _same_bytes(got_d, want_d) and _same_bytes(got_i, want_i), "side stream"
-    assert all(_same_bytes(x, y) for x, y in zip(a.read(), (avg, sup))), "side stream"
-    s, a = Search(z, K), Average(stack, cover, index, weight)
-    graph = torch.cuda.CUDAGraph()
-    torch.cuda.synchronize()
-    with torch.cuda.graph(graph):
-        st = ctypes.c_void_p(torch.cuda.current_stream(_dev()).cuda_stream)
-        s.run(chunks, st=st)
-        assert a.call(st=st) == 0
-    for _ in range(2):
-        s.refill()
-        a.average.fill_byte(0)
-        graph.replay()
-        got_d, got_i = s.read()
-        assert _same_bytes(got_d, want_d) and _same_bytes(got_i, want_i), "graph replay"
-        assert all(_same_bytes(x, y) for x, y in zip(a.read(), (avg, sup))), "graph replay"
-
-
+# ---------------------------------------------------------------- both entries: refusals, the wrappers
 def test_every_refusal_leaves_the_buffers_untouched():
     """Every SVAE_E_INVALID case of the header, one call each: the status, a message in svae_last_error, and afterwards every
     output still holds its fill inside intact guards; the same buffers are then accepted as they stand."""

@@ -1,6 +1,6 @@
-"""CPU-only: the binding of include/svae_neighbours.h held to that header (and kept out of _lib.HEADERS, PENDING_HEADERS and
-BOUND_SIGNATURES), the float64 reference of the neighbour kernels (tests/neighbours_ref.py) held to a brute-force sort on a
-fixture full of ties, and neighbours.py's command line: its defaults and every refusal that needs no GPU."""
+"""CPU-only: what is include/svae_neighbours.h's own in its binding, the float64 reference of the neighbour kernels
+(tests/neighbours_ref.py) held to a brute-force sort on a fixture full of ties, and neighbours.py's command line: its defaults
+and every refusal that needs no GPU."""
 import json
 import os
 import subprocess
@@ -10,68 +10,31 @@ import numpy as np
 import pytest
 
 import neighbours_ref as R
-from test_binding_cpu import _allowed, binding_constants, parse_header
+from test_binding_cpu import binding_constants, parse_added_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ELEVEN = ["svae.h", "svae_stream.h", "svae_align.h", "svae_ctfcorr.h", "svae_cluster.h", "svae_frc.h", "svae_refine.h",
-          "svae_classify.h", "svae_gmm.h", "svae_expect.h", "svae_pca.h"]
 
 
 # ---------------------------------------------------------------- the header and its table
 def test_neighbour_binding_matches_its_header():
-    """include/svae_neighbours.h against _lib.NEIGHBOUR_SIGNATURES, both ways and type by type, with the parser and the type
-    rules tests/test_binding_cpu.py uses for svae.h; the argument names in order; the header's one constant is
-    NEIGHBOUR_LIMITS; the loaded library has both entries with the table's types, and ops._POINTER_ARGS knows the device
-    pointers."""
+    """What is include/svae_neighbours.h's own (the rules every added header shares are tests/test_binding_cpu.py's): two
+    functions and their argument names, no struct; the header's one constant is _lib.NEIGHBOUR_LIMITS, and none of this adds an
+    upper-case integer to the binding; the positions of the device pointers."""
     from spatial_vae_amd import _lib, ops
-    path = os.path.join(ROOT, "include", "svae_neighbours.h")
-    with open(path) as f:
-        text = f.read()
-    H = parse_header(text.replace('#include "svae.h"', ""))
+    H = parse_added_header("svae_neighbours.h")[1]
+    assert _lib.HEADERS["svae_neighbours.h"] is _lib.NEIGHBOUR_SIGNATURES
     assert H["structs"] == {} and len(H["functions"]) == 2
     assert H["constants"] == {"SVAE_NBR_" + k.upper(): v for k, v in _lib.NEIGHBOUR_LIMITS.items()} == {"SVAE_NBR_MAX_K": 256}
     assert _lib.NEIGHBOUR_LIMITS == {"max_k": 256} and R.MAX_K == 256 and R.MAX_T == 257
-    assert set(H["functions"]) == set(_lib.NEIGHBOUR_SIGNATURES) == set(_lib.declared_in_header(path))
-    for name, ((rbase, rptr), args) in H["functions"].items():
-        restype, argtypes = _lib.NEIGHBOUR_SIGNATURES[name]
-        assert restype in _allowed(rbase, rptr, _lib), name
-        assert len(args) == len(argtypes), name
-        for (base, pointer, arg), have in zip(args, argtypes):
-            assert have in _allowed(base, pointer, _lib), (name, arg)
-        assert args[-1][2] == "stream", name
     names = {k: [a[2] for a in v[1]] for k, v in H["functions"].items()}
     assert names["svae_nbr_search"] == ["query", "B", "query_base", "cand", "M", "cand_base", "D", "K", "best_d2", "best_index",
                                         "stream"]
     assert names["svae_nbr_average"] == ["stack", "cover", "images", "N", "C", "index", "weight", "B", "T", "average", "support",
                                          "stream"]
     assert not [k for k in binding_constants(_lib) if "NBR" in k or "NEIGHBOUR" in k]
-    L = _lib.lib()
-    for name, (restype, argtypes) in _lib.NEIGHBOUR_SIGNATURES.items():
-        fn = getattr(L, name)
-        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
-    assert L.svae_abi_version() == 2
     assert ops._POINTER_ARGS["svae_nbr_search"] == (0, 3, 8, 9)
     assert ops._POINTER_ARGS["svae_nbr_average"] == (0, 1, 5, 6, 9, 10)
     assert ops.NeighbourSearch.MAX_K == 256
-
-
-def test_the_table_waits_in_a_third_dict_and_the_build_sees_the_header():
-    """svae_neighbours.h is the one row of WAITING_HEADERS; HEADERS has the eleven headers it had, PENDING_HEADERS svae_eigen.h
-    alone and BOUND_SIGNATURES exactly those two tables, so the shared stream table is asked for nothing new; an edit of the
-    header or of csrc/neighbours.h makes the library stale."""
-    import spatial_vae_amd  # noqa: F401
-    from spatial_vae_amd import _lib
-    build = sys.modules["spatial_vae_amd.build"]
-    assert _lib.WAITING_HEADERS == {"svae_neighbours.h": _lib.NEIGHBOUR_SIGNATURES} and len(_lib.WAITING_HEADERS) == 1
-    assert list(_lib.HEADERS) == ELEVEN
-    assert _lib.PENDING_HEADERS == {"svae_eigen.h": _lib.EIGEN_SIGNATURES}
-    assert set(_lib.ALL_SIGNATURES) == {n for t in _lib.HEADERS.values() for n in t}
-    assert set(_lib.BOUND_SIGNATURES) == set(_lib.ALL_SIGNATURES) | set(_lib.EIGEN_SIGNATURES)
-    assert not [n for n in _lib.BOUND_SIGNATURES if n.startswith("svae_nbr_")]
-    deps = [os.path.normpath(d) for d in build.dependencies()]
-    assert os.path.join(ROOT, "include", "svae_neighbours.h") in deps
-    assert os.path.join(ROOT, "spatial_vae_amd", "csrc", "neighbours.h") in deps
-    assert all(os.path.isfile(d) for d in deps)
 
 
 # ---------------------------------------------------------------- the reference against brute force

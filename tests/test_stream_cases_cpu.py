@@ -13,7 +13,8 @@ def test_the_table_covers_exactly_the_entry_points_that_take_a_stream():
     """The names are derived from _lib.ALL_SIGNATURES, the signature tables of every header of _lib.HEADERS (status returned,
     last argument a bare address), never typed: a new export that takes a stream fails here until it has a case."""
     derived = S.stream_entry_points()
-    assert len(derived) >= 42 and "svae_decoder_backward" in derived and "svae_wiener_finish" in derived
+    assert len(derived) >= 50 and "svae_decoder_backward" in derived and "svae_wiener_finish" in derived
+    assert "svae_eig_rotate" in derived and "svae_nbr_average" in derived
     assert "svae_profile_read" not in derived and "svae_saved_bytes" not in derived
     assert S.covered_entry_points() == derived
     assert set(derived) <= set(_lib.ALL_SIGNATURES)
@@ -72,6 +73,14 @@ def test_integer_inputs_are_valid_in_both_sets():
             if "target" in i and i["target"].dtype == np.int32:     # svae_expect.h: outside [0, n_classes) is folded into no class
                 assert i["target"].shape == (case.n_ref,) and (i["target"] >= 0).all()
                 assert set(range(case.n_classes)) <= set(i["target"].tolist())
+            if "class_of" in i:                             # svae_eigen.h: outside [0, K) is an image in no class
+                live = (i["class_of"] >= 0) & (i["class_of"] < case.K)
+                assert live.sum() >= 2 and -1 in i["class_of"] and (i["class_of"] >= case.K).any()
+                assert i["members"].tolist() == [int((i["class_of"] == k).sum()) for k in range(case.K)]
+            if "slots" in i:                                # svae_neighbours.h: outside [0, images) is skipped
+                live = (i["slots"] >= 0) & (i["slots"] < case.images)
+                assert live.any() and -1 in i["slots"] and (i["slots"] >= case.images).any()
+                assert i["stack"].shape[0] == case.images and (i["index"] == -1).all() and np.isposinf(i["d2"]).all()
     g = S.Guard()
     assert np.isfinite(g.inputs(0)["grad"]).all() and np.isinf(g.inputs(1)["grad"]).sum() == 1
     assert np.isfinite(g.inputs(1, finite=True)["grad"]).all()
